@@ -1,7 +1,14 @@
 """Benchmark of the particle forward-simulation hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`, the roofline of the timed launches).  `--dump-outputs DIR` also writes the
+outcomes of the last timed step (what a caller of the timed path receives) as DIR/<name>.npy.
+Everything that takes runs of its own (the CPU baseline, the host-buffer call, the pipelined
+batches, the strong-scaling projection, the batched configuration check) is measured only
+with `--full`, where the `--no-*` options still switch single legs off.
 
 `--gpus N` (N > 1) without a launcher starts the N rank processes itself (spawn_ranks);
 under a launcher WORLD_SIZE must equal N.  A "step" is one ForwardSimulateRobots batch
@@ -15,9 +22,9 @@ wall time of the K timed steps (weak scaling: each GPU owns 65,536 particles; RN
 streams are keyed by global particle id so shards are independent).
 
 Also reported: the dominant kernel's roofline (algorithmic SDF bytes per launch / the
-launch's HIP-event duration, against the 8 TB/s HBM peak) and the CPU baseline (the
-oracle, a C++ restatement of the reference's OpenMP path, timed on this host on a
-bounded prefix of the same workload).
+launch's HIP-event duration, against the 8 TB/s HBM peak) and, with `--full`, the CPU
+baseline (the oracle, a C++ restatement of the reference's OpenMP path, timed on this
+host on a bounded prefix of the same workload).
 """
 from __future__ import annotations
 
@@ -35,6 +42,7 @@ UNIT = "particle-microsteps/s"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md (8.0 TB/s spec)
 FP64_VECTOR_PEAK_TFLOPS = 78.6  # MI355X FP64 vector peak, AMD's public spec (not in the container guide)
 PARTICLES_PER_GPU = 65536
+DUMP_BYTES = 60 << 20  # --dump-outputs writes at most this much (array data; the .npy headers are 128 bytes each)
 # the other BASELINE.json configs, runnable with --workload for side measurements
 # (the headline line is cfg3): base particle count of the config, default per GPU, description
 WORKLOADS = {
@@ -150,6 +158,26 @@ def config_check_bench(sim, wl, dev, n=1 << 20, reps=3, cpu_sample=16384, thread
     return out
 
 
+def dump_outputs(directory: str, outcomes: dict) -> None:
+    """`--dump-outputs DIR`: the last timed step's outcomes, one float64 array per name
+    (positions (n, W); collided, microsteps, resolver_iterations, error_flags (n,)), every
+    particle in global id order.  The inputs are seeded and step k uses RNG call index k, so
+    the same arguments give the same arrays from run to run and from build to build.  At most
+    DUMP_BYTES are written: of a larger batch a fixed (seeded) sample of the particles, whose
+    ids are written as particle_ids."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    n, w = outcomes["positions"].shape
+    ids = np.arange(n)
+    rows = DUMP_BYTES // ((w + 5) * 8)
+    if n > rows:
+        ids = np.sort(np.random.default_rng(0).choice(n, size=rows, replace=False))
+    np.save(os.path.join(directory, "particle_ids.npy"), ids.astype(np.float64))
+    for name in ("positions", "collided", "microsteps", "resolver_iterations", "error_flags"):
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(outcomes[name][ids], dtype=np.float64))
+
+
 def kernel_name(kind: str, robot_type: int, spec) -> str:
     """The simulation kernel the last timed launch ran (fks_get_launch_info's last_kernel),
     not the one the flags asked for."""
@@ -231,7 +259,17 @@ def main():
                     help="skip the strong-scaling projection (the batch's 2/4/8-way shards timed alone on this GPU)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / shard / gather check without a GPU (gloo): no simulation, value null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outcomes of the last timed step (positions, collided, "
+                         "microsteps, resolver_iterations, error_flags of every particle, float64) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline, the host-buffer call, the pipelined "
+                         "batches, the strong-scaling projection and the batched configuration check (each still "
+                         "switched off by its --no-* option); off by default, so a plain run times the steps only")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_config_check = args.no_projection = True
+        args.pipeline_batches = 0
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus < 1:
@@ -270,7 +308,7 @@ def main():
     from fast_kinematic_simulator_amd import workloads as W
 
     from fast_kinematic_simulator_amd._capi import PHASE_COUNTS
-    from fast_kinematic_simulator_amd.sharding import gather_outcomes, pack_outcomes, shard_bounds
+    from fast_kinematic_simulator_amd.sharding import gather_outcomes, pack_outcomes, shard_bounds, unpack_outcomes
 
     base, per_gpu, workload_desc = WORKLOADS[args.workload]
     n_total = (args.particles or per_gpu) * world
@@ -328,8 +366,10 @@ def main():
         # outcome of every particle -> rank 0 (RCCL gather over xGMI)
         pack_outcomes(out_q, out_coll, out_micro, out_res, out_err, out=packed)
         if dist is not None:
-            gather_outcomes(packed, dist, n_total, world, rank, gathered)
+            return gather_outcomes(packed, dist, n_total, world, rank, gathered)
+        return packed
 
+    outcomes = None
     for w in range(args.warmup):
         step(1000 + w)
     torch.cuda.synchronize()
@@ -342,12 +382,15 @@ def main():
     torch.cuda.synchronize()
     t_start = time.perf_counter()
     for k in range(args.steps):
-        step(k, events[k])
+        outcomes = step(k, events[k])
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0 and outcomes is not None:
+        # before anything else runs: the side measurements below reuse the output buffers
+        dump_outputs(args.dump_outputs, unpack_outcomes(outcomes))
     kernel_ms = [a.elapsed_time(b) for a, b in events]
     ran_kernel = sim.launch_info()["last_kernel"]  # what the last timed launch actually ran
     tot = sim.total_counters()
@@ -392,12 +435,14 @@ def main():
         value = all_micro / elapsed
         # the host-buffer entry (fks_forward_simulate: starts/targets over PCIe, outcomes
         # back) on the same batch: reported beside `value`, never as it
-        sim.set_call_index(0)
-        t0 = time.perf_counter()
-        hr = sim.forward_simulate_arrays(wl.robot, wl.starts[lo:lo + n_local], wl.targets, True)
-        host_s = time.perf_counter() - t0
-        pcie = {"value": float(np.sum(hr["microsteps"], dtype=np.int64)) / host_s, "unit": UNIT, "ms": host_s * 1e3,
-                "note": "one fks_forward_simulate call with host buffers (H2D starts/targets, kernel, D2H outcomes), rank 0"}
+        pcie = None
+        if args.full:
+            sim.set_call_index(0)
+            t0 = time.perf_counter()
+            hr = sim.forward_simulate_arrays(wl.robot, wl.starts[lo:lo + n_local], wl.targets, True)
+            host_s = time.perf_counter() - t0
+            pcie = {"value": float(np.sum(hr["microsteps"], dtype=np.int64)) / host_s, "unit": UNIT, "ms": host_s * 1e3,
+                    "note": "one fks_forward_simulate call with host buffers (H2D starts/targets, kernel, D2H outcomes), rank 0"}
         pipe = None
         if world == 1 and not args.no_contacts:
             try:
@@ -658,6 +703,8 @@ def in_process(args) -> int:
         for key in totals:
             totals[key] += c[key] if key != "calls" else 1
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, r)
     assert micro == totals["microsteps"], (micro, totals["microsteps"])
     avg_kernel_s = sum(kernel_ms) / len(kernel_ms) / 1e3
     bytes_per_device_launch = totals["sdf_bytes"] / totals["calls"] / ndev

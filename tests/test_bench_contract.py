@@ -1,5 +1,6 @@
 """bench.py keeps the driver's contract: one JSON line with the BASELINE.json metric,
-whole-job value, roofline and cpu_baseline objects (GPU: a small run end to end)."""
+whole-job value and roofline, with `--full` also the cpu_baseline object and the other side
+measurements (GPU: a small run end to end)."""
 import json
 import os
 import subprocess
@@ -14,14 +15,49 @@ def test_bench_cli_parses():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=120)
     assert p.returncode == 0 and "--workload" in p.stdout and "--gpus" in p.stdout
+    assert "--full" in p.stdout and "--dump-outputs" in p.stdout
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_only_and_dumps_outputs(tmp_path):
+    """Without `--full` nothing but the timed steps is measured (the side objects are null), the
+    line keeps the headline keys, and `--dump-outputs` writes the last timed step's outcomes:
+    one float64 array per outcome, every particle, consistent with the line's own counts."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    p = _run_bench(["--gpus", "1", "--particles", "2048", "--steps", "1", "--warmup", "1", "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = _json_lines(p.stdout)
+    assert len(lines) == 1
+    d = lines[0]
+    with open(os.path.join(ROOT, "BASELINE.json")) as f:
+        assert d["metric"] == json.load(f)["metric"]
+    assert d["value"] > 0 and d["unit"] == "particle-microsteps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 1 and d["ms_per_step"] > 0
+    # value = microsteps of the timed steps / their wall time
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - d["config"]["microsteps_per_step"]) < 1e-6 * d["config"]["microsteps_per_step"]
+    for side in ("cpu_baseline", "config_check", "pcie_inclusive", "pipelined", "strong_scaling_projection"):
+        assert d[side] is None, side
+    assert d["roofline"]["avg_kernel_ms"] > 0 and d["specialization"]["all_timed_launches"] is True
+    arrays = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(arrays) == ["collided", "error_flags", "microsteps", "particle_ids", "positions", "resolver_iterations"]
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    assert arrays["positions"].shape == (2048, 7) and np.isfinite(arrays["positions"]).all()
+    assert all(arrays[k].shape == (2048,) for k in arrays if k != "positions")
+    assert np.array_equal(arrays["particle_ids"], np.arange(2048))
+    assert set(np.unique(arrays["collided"])) <= {0.0, 1.0} and not arrays["error_flags"].any()
+    # one timed step: the dumped step is the one the line counts
+    assert arrays["microsteps"].min() >= 1 and arrays["microsteps"].sum() == d["config"]["microsteps_per_step"]
+    assert arrays["resolver_iterations"].sum() == d["config"]["resolver_iterations_per_step"] > 0
 
 
 @pytest.mark.gpu
 def test_bench_json_line():
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
         metric = json.load(f)["metric"]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--particles", "2048", "--steps", "1", "--warmup", "1",
-                        "--cpu-sample", "16", "--no-config-check"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--particles", "2048", "--steps", "1",
+                        "--warmup", "1", "--cpu-sample", "16", "--no-config-check"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]

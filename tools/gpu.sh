@@ -43,7 +43,7 @@ export FKS_SHAPEC=$PWD/fast_kinematic_simulator_amd/fks_shapec
 # (warm), so no compiler process starts under rocprofv3
 export FKS_KERNEL_CACHE=/tmp/fks_kernel_cache_$TAG
 warm() { timeout -k 10 300 "$@" > /dev/null 2>&1; }
-BP="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --pipeline-batches 0 --no-projection"
+BP="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --pipeline-batches 0 --no-projection"
 lib() { [ "$1" = L ] && echo $L || echo "$1"; }
 
 run_task() {
@@ -53,8 +53,8 @@ run_task() {
   tests:*) f=${1#tests:}; timeout -k 10 600 python -u -m pytest tests/$f.py -m gpu -x -v --timeout 200 --timeout-method thread > $O/${TAG}_pytest_$f.log 2>&1 ;;
   testslib:*) spec=${1#testslib:}; f=${spec%%:*}; l=$(lib ${spec#*:}); FKS_LIB_PATH=$PWD/$l FKS_VARIANT_LIB=1 timeout -k 10 600 python -u -m pytest tests/$f.py -m gpu -x -v --timeout 200 --timeout-method thread > $O/${TAG}_pytest_${f}_$(basename $l .so).log 2>&1 ;;
   smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1 ;;
-  bench) timeout -k 10 400 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err ;;
-  bench:*) w=${1#bench:}; timeout -k 10 300 python bench.py --workload $w --no-config-check > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err ;;
+  bench) timeout -k 10 400 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err ;;
+  bench:*) w=${1#bench:}; timeout -k 10 300 python bench.py --full --workload $w --no-config-check > $O/${TAG}_bench_$w.json 2> $O/${TAG}_bench_$w.err ;;
   others) for w in cfg1 cfg2 cfg4 cfg5; do run_task bench:$w || return $?; done ;;
   trace) warm $BP && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace -o bench -- $BP > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_trace.err ;;
   pmc)
@@ -63,13 +63,13 @@ run_task() {
     timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/${TAG}_pmc_write -o bench -- $BP > /dev/null 2> $O/${TAG}_pmc_write.err &&
     timeout -s KILL 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $O/${TAG}_pmc_tcc -o bench -- $BP > /dev/null 2> $O/${TAG}_pmc_tcc.err ;;
   pmc:*)
-    w=${1#pmc:}; BW="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-config-check --pipeline-batches 0 --no-projection --workload $w"
+    w=${1#pmc:}; BW="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-config-check --pipeline-batches 0 --no-projection --workload $w"
     warm $BW &&
     timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${TAG}_pmc_${w}_fetch -o bench -- $BW > /dev/null 2> $O/${TAG}_pmc_${w}_fetch.err &&
     timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/${TAG}_pmc_${w}_write -o bench -- $BW > /dev/null 2> $O/${TAG}_pmc_${w}_write.err &&
     timeout -s KILL 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $O/${TAG}_pmc_${w}_tcc -o bench -- $BW > /dev/null 2> $O/${TAG}_pmc_${w}_tcc.err ;;
   valu)
-    B1="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-config-check --pipeline-batches 0 --no-projection"
+    B1="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-config-check --pipeline-batches 0 --no-projection"
     mkdir -p $O/${TAG}_valu
     warm $B1 &&
     timeout -s KILL 180 rocprofv3 --pmc VALUBusy --kernel-trace --output-format csv -d $O/${TAG}_valu/valubusy -o bench -- $B1 > /dev/null 2> $O/${TAG}_valu/valubusy.err &&
@@ -77,7 +77,7 @@ run_task() {
     timeout -s KILL 180 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/${TAG}_valu/issue -o bench -- $B1 > /dev/null 2> $O/${TAG}_valu/issue.err ;;
   counters) timeout -k 10 120 rocprofv3 --list-avail > $O/${TAG}_counters.txt 2>&1 ;;
   icache)
-    B1="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-config-check --pipeline-batches 0 --no-projection"
+    B1="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-config-check --pipeline-batches 0 --no-projection"
     mkdir -p $O/${TAG}_icache
     warm $B1 &&
     timeout -s KILL 180 rocprofv3 --pmc SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/${TAG}_icache/ic -o bench -- $B1 > /dev/null 2> $O/${TAG}_icache/ic.err ;;
@@ -104,7 +104,7 @@ run_task() {
     rc=$?; unset FKS_LIB_PATH FKS_VARIANT_LIB; return $rc ;;
   mix:*)
     spec=${1#mix:}; w=${spec%%:*}; l=$(lib ${spec#*:}); n=$(basename $l .so); D=$O/${TAG}_mix_${w}_$n
-    BM="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-config-check --pipeline-batches 0 --no-projection --workload $w"
+    BM="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-config-check --pipeline-batches 0 --no-projection --workload $w"
     export FKS_LIB_PATH=$PWD/$l FKS_VARIANT_LIB=1
     warm $BM &&
     timeout -s KILL 240 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_INSTS_BRANCH SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $D/mix -o m -- $BM > $D.mix.log 2>&1 &&
@@ -116,8 +116,8 @@ run_task() {
     [ "$rest" != "$heavy" ] && rel=${rest#*:}
     np=""; [ "$w" = cfg4 -o "$w" = cfg5 ] && np="--particles 131072"
     timeout -k 10 600 python tools/sched_sweep.py --workload $w $np --segments $seg --heavy $heavy --prio 1 --rel $rel --json $O/${TAG}_sched_$w.json > $O/${TAG}_sched_$w.log 2>&1 ;;
-  inproc:*) d=${1#inproc:}; timeout -k 10 400 python bench.py --in-process --devices $d --steps 3 --warmup 1 --no-cpu-baseline > $O/${TAG}_inproc_${d//,/}.json 2> $O/${TAG}_inproc_${d//,/}.err ;;
-  torchrun1) timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline > $O/${TAG}_torchrun_w1.json 2> $O/${TAG}_torchrun_w1.err ;;
+  inproc:*) d=${1#inproc:}; timeout -k 10 400 python bench.py --full --in-process --devices $d --steps 3 --warmup 1 --no-cpu-baseline > $O/${TAG}_inproc_${d//,/}.json 2> $O/${TAG}_inproc_${d//,/}.err ;;
+  torchrun1) timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline > $O/${TAG}_torchrun_w1.json 2> $O/${TAG}_torchrun_w1.err ;;
   round) for t in suite smoke bench trace pmc others; do run_task $t || return $?; done ;;
   *) echo "unknown task $1" >&2; return 2 ;;
   esac

@@ -2,7 +2,7 @@
 
 Usage (after the three passes FETCH_SIZE / WRITE_SIZE / TCC_HIT_sum+TCC_MISS_sum,
 each its own `rocprofv3 --pmc ... --kernel-trace --output-format csv` run of
-`python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline`):
+`python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline`):
 
     python tools/profile_pmc.py gpurun_out/pmc_fetch gpurun_out/pmc_write gpurun_out/pmc_tcc r01
     python tools/profile_pmc.py <fetch> <write> <tcc> r04_cfg5 fks_simulate_linked_lean   # another kernel
