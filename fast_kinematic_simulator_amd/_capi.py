@@ -221,7 +221,7 @@ class LaunchInfo(ctypes.Structure):
 
 
 KERNEL_KINDS = {0: "none", 1: "throughput", 2: "small_batch", 3: "shaped", 4: "traced", 5: "individual", 6: "cooperative",
-                7: "shaped_small_batch"}
+                7: "shaped_small_batch", 8: "path", 9: "path_small_batch"}
 
 
 class Trace(ctypes.Structure):
@@ -283,6 +283,18 @@ PROTOTYPES = [
         c_int32,
         [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_uint64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_int32],
+    ),
+    (
+        "fks_forward_simulate_path",
+        c_int32,
+        [c_void_p, POINTER(c_double), c_uint64, POINTER(c_double), c_uint64, c_uint64, c_int32, POINTER(c_double), POINTER(c_uint8),
+         POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)],
+    ),
+    (
+        "fks_forward_simulate_path_device",
+        c_int32,
+        [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_uint64, c_uint64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_int32],
     ),
     (
         "fks_forward_simulate_traced",
@@ -358,6 +370,12 @@ PROTOTYPES = [
         "fks_multi_forward_simulate",
         c_int32,
         [c_void_p, POINTER(c_double), c_uint64, POINTER(c_double), c_uint64, c_int32, POINTER(c_double), POINTER(c_uint8),
+         POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)],
+    ),
+    (
+        "fks_multi_forward_simulate_path",
+        c_int32,
+        [c_void_p, POINTER(c_double), c_uint64, POINTER(c_double), c_uint64, c_uint64, c_int32, POINTER(c_double), POINTER(c_uint8),
          POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)],
     ),
     ("fks_multi_get_statistics", c_int32, [c_void_p, POINTER(Statistics)]),

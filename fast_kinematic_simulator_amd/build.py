@@ -179,5 +179,11 @@ def build_planner_test(force: bool = False, workspace: bool = False) -> str:
     return build_cpp_program(os.path.join("tests", "cpp", "planner_interface_test.cpp"), "planner_interface_test", force)
 
 
+def build_path_test(force: bool = False) -> str:
+    """Compile tests/cpp/path_interface_test.cpp: ForwardSimulateRobotsAlongPath against the
+    chained ForwardSimulateRobots calls on a scene built in code."""
+    return build_cpp_program(os.path.join("tests", "cpp", "path_interface_test.cpp"), "path_interface_test", force)
+
+
 if __name__ == "__main__":
     print(build_library(force=True, verbose=True))

@@ -45,6 +45,13 @@ extern "C" __global__ void fks_simulate_se3_coop(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_linked_lean(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_linked_lean_indiv(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_linked_lean_traced(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_path(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_lean_path(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se2_path(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se3_path(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_path_small(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se2_path_small(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se3_path_small(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_linked(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se2(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se3(const fksd::SimArgs* args);
@@ -92,6 +99,22 @@ sim_kernel_t small_kernel_for(int robot_type) {
         case FKS_ROBOT_SE2: return fks_simulate_se2_small;
         case FKS_ROBOT_SE3: return fks_simulate_se3_small;
         default: return fks_simulate_linked_small;
+    }
+}
+
+/* the waypoint-path instantiations (fks_forward_simulate_path): throughput and small-batch budget */
+sim_kernel_t path_kernel_for(int robot_type, bool lean) {
+    switch (robot_type) {
+        case FKS_ROBOT_SE2: return fks_simulate_se2_path;
+        case FKS_ROBOT_SE3: return fks_simulate_se3_path;
+        default: return lean ? fks_simulate_linked_lean_path : fks_simulate_linked_path;
+    }
+}
+sim_kernel_t path_small_kernel_for(int robot_type) {
+    switch (robot_type) {
+        case FKS_ROBOT_SE2: return fks_simulate_se2_path_small;
+        case FKS_ROBOT_SE3: return fks_simulate_se3_path_small;
+        default: return fks_simulate_linked_path_small;
     }
 }
 
@@ -272,6 +295,9 @@ struct fks_context {
     unsigned long long* h_counters = nullptr; /* pinned */
     fksd::SimArgs* d_args = nullptr;          /* kernel arguments, read through a pointer */
     fksd::SimArgs* h_args = nullptr;          /* pinned staging for d_args */
+    fksd::SimArgs* d_path_args = nullptr;     /* a path call's records, one per leg (SimArgs.path_legs) */
+    fksd::SimArgs* h_path_args = nullptr;     /* pinned staging for d_path_args */
+    size_t cap_path_args = 0;
     bool pending = false;
     int pending_kind = 0; /* 0 = forward simulation, 1 = batched config check */
     hipStream_t pending_stream = nullptr;
@@ -678,6 +704,8 @@ void fks_destroy(fks_context* ctx) {
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->d_args) (void)hipFree(ctx->d_args);
     if (ctx->h_args) (void)hipHostFree(ctx->h_args);
+    if (ctx->d_path_args) (void)hipFree(ctx->d_path_args);
+    if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     delete ctx;
@@ -1251,7 +1279,10 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
                                   uint64_t num_targets, uint64_t first_particle_id, int32_t allow_contacts,
                                   double* d_out_positions, uint8_t* d_out_collided, uint32_t* d_out_microsteps,
                                   uint32_t* d_out_resolver_iterations, uint32_t* d_out_error_flags, void* stream,
-                                  int32_t synchronize, const TraceDev* tr, double* d_pid_io = nullptr) {
+                                  int32_t synchronize, const TraceDev* tr, double* d_pid_io = nullptr, uint64_t path_legs = 0) {
+    /* path_legs > 0: fks_forward_simulate_path (d_targets holds the waypoints, the outputs are
+     * leg-major); 0: a plain call */
+    const bool path = path_legs > 0;
     if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
     if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
     if (n > 0 && (!d_starts || !d_targets || !d_out_positions))
@@ -1259,15 +1290,26 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     if (n > 0 && num_targets != 1 && num_targets != n)
         return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "targets must be 1 or n (SPCS:792)");
     if (n > 0xffffffffull) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per call");
+    if (path) {
+        /* seg_done counts a particle's segments over all legs in 31 bits (the top bit marks a claim) */
+        const uint32_t T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
+        const uint32_t k = std::min(ctx->segment_steps ? ctx->segment_steps : kDefaultSegmentSteps, T);
+        const bool segmented = ctx->segment_steps != 0 || n > (uint64_t)ctx->grid_waves; /* as below */
+        const uint64_t nseg = segmented ? ((uint64_t)T - 1u) / k + 1u : 1u;
+        if (path_legs >= (1ull << 31) || path_legs * nseg >= (1ull << 31))
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "legs x segments per leg must stay below 2^31");
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     fks_status st = settle(ctx);
     if (st != FKS_OK) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ctx->call_start = std::chrono::steady_clock::now();
-    const uint64_t key = splitmix64(ctx->seed ^ splitmix64(ctx->call_index));
-    ctx->call_index++;
+    const uint64_t first_call = ctx->call_index;
+    const uint64_t key = splitmix64(ctx->seed ^ splitmix64(first_call));
+    ctx->call_index += path ? path_legs : 1u;
     std::memset(&ctx->last, 0, sizeof(ctx->last));
-    ctx->last.particles = n;
+    ctx->last.particles = path ? n * path_legs : n; /* a path's counters are its chain's sums */
+    if (path && n == 0) return FKS_OK; /* the chain's calls would launch nothing either */
     fksd::SimArgs a;
     std::memset(&a, 0, sizeof(a));
     a.sdf_g = ctx->sdf_g;
@@ -1329,7 +1371,17 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
         a.seg_heavy_resolver = (uint32_t)std::min<uint64_t>(heavy, 0xffffffffull);
         a.seg_heavy_prio = ctx->heavy_priority;
         /* the relative test's running sums pack 24 bits of segments: off for larger batches */
-        a.seg_heavy_rel = ((uint64_t)n * a.nseg < (1ull << 24)) ? ctx->heavy_relative : 0u;
+        a.seg_heavy_rel = ((uint64_t)n * a.nseg * (path ? path_legs : 1u) < (1ull << 24)) ? ctx->heavy_relative : 0u;
+    }
+    /* a path's segment space is path_legs x nseg, so seg_done is needed from two legs on */
+    const uint64_t segments = (uint64_t)a.nseg * (path ? path_legs : 1u);
+    if (segments > 1 && a.nseg == 1) {
+        if (n > ctx->cap_seg_done) {
+            HIP_TRY(ctx, ensure(&ctx->d_seg_done, (size_t)n));
+            ctx->cap_seg_done = (size_t)n;
+        }
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_seg_done, 0, (size_t)n * sizeof(uint32_t), s));
+        a.seg_done = ctx->d_seg_done;
     }
     if (a.nseg > 1) {
         const size_t words = (size_t)n * a.seg_stride;
@@ -1355,34 +1407,71 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
         a.tr_step_cap = tr->step_cap;
         a.tr_cfg_cap = tr->cfg_cap;
     }
-    /* the previous call has settled, so the pinned staging copy is free */
-    *ctx->h_args = a;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_args, ctx->h_args, sizeof(a), hipMemcpyHostToDevice, s));
+    /* a batch that fits the small-batch kernel's resident waves, whole particles, plain
+     * simulation: that kernel (every particle has its wave from the start either way) */
+    const bool coop = !path && ctx->small_batch && ctx->cooperative && !tr && !ctx->individual_jacobians && !ctx->lean &&
+                      a.nseg == 1 && n > 0 && n <= (uint64_t)ctx->coop_particles;
+    const bool small = !coop && ctx->small_batch && !tr && !ctx->individual_jacobians && !ctx->lean && a.nseg == 1 &&
+                       n <= (uint64_t)ctx->small_grid_waves;
+    const fksd::SimArgs* d_launch_args = ctx->d_args;
+    /* the previous call has settled, so the pinned staging copies are free */
+    if (path) {
+        /* one record per leg: the same call except for the leg's key (the chain's call index),
+         * waypoints, start configurations (the leg before's output slice) and output slices */
+        if (path_legs > ctx->cap_path_args) {
+            if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
+            ctx->h_path_args = nullptr;
+            ctx->cap_path_args = 0;
+            HIP_TRY(ctx, ensure(&ctx->d_path_args, (size_t)path_legs));
+            HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_path_args, (size_t)path_legs * sizeof(fksd::SimArgs), 0));
+            ctx->cap_path_args = (size_t)path_legs;
+        }
+        const uint64_t W = (uint64_t)ctx->R.W;
+        a.path_legs = (uint32_t)path_legs;
+        /* whole legs and a wave for every particle: the wave keeps its particle through all legs */
+        a.path_carry = (a.nseg == 1 && n <= (uint64_t)(small ? ctx->small_grid_waves : ctx->grid_waves)) ? 1u : 0u;
+        for (uint64_t leg = 0; leg < path_legs; ++leg) {
+            fksd::SimArgs& r = ctx->h_path_args[leg];
+            r = a;
+            const uint64_t leg_key = splitmix64(ctx->seed ^ splitmix64(first_call + leg));
+            r.key0 = (uint32_t)leg_key;
+            r.key1 = (uint32_t)(leg_key >> 32);
+            r.targets = d_targets + leg * num_targets * W;
+            r.starts = leg == 0 ? d_starts : d_out_positions + (leg - 1) * n * W;
+            r.out_q = d_out_positions + leg * n * W;
+            r.out_collided = d_out_collided ? d_out_collided + leg * n : nullptr;
+            r.out_micro = d_out_microsteps ? d_out_microsteps + leg * n : nullptr;
+            r.out_resolver = d_out_resolver_iterations ? d_out_resolver_iterations + leg * n : nullptr;
+            r.out_err = d_out_error_flags ? d_out_error_flags + leg * n : nullptr;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path_args, ctx->h_path_args, (size_t)path_legs * sizeof(fksd::SimArgs),
+                                    hipMemcpyHostToDevice, s));
+        d_launch_args = ctx->d_path_args;
+    } else {
+        *ctx->h_args = a;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_args, ctx->h_args, sizeof(a), hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, fksd::kCounterWords * sizeof(unsigned long long), s));
     const uint64_t groups_needed = (n + ctx->waves_per_group - 1) / ctx->waves_per_group;
     const uint32_t grid = (uint32_t)((groups_needed < (uint64_t)ctx->grid_groups) ? (groups_needed > 0 ? groups_needed : 1)
                                                                                   : ctx->grid_groups);
-    /* a batch that fits the small-batch kernel's resident waves, whole particles, plain
-     * simulation: that kernel (every particle has its wave from the start either way) */
-    const bool coop = ctx->small_batch && ctx->cooperative && !tr && !ctx->individual_jacobians && !ctx->lean && a.nseg == 1 && n > 0 &&
-                      n <= (uint64_t)ctx->coop_particles;
-    const bool small = !coop && ctx->small_batch && !tr && !ctx->individual_jacobians && !ctx->lean && a.nseg == 1 &&
-                       n <= (uint64_t)ctx->small_grid_waves;
     /* the plain throughput path runs the robot's shape-specialised kernel: built (or fetched
      * from a cache) here at the first such launch; a failure keeps the generic kernel and is
      * reported by fks_get_specialization / fks_get_last_error, not by this call */
-    if (ctx->spec_pending && !tr && !small && !coop && !ctx->individual_jacobians) {
+    if (ctx->spec_pending && !path && !tr && !small && !coop && !ctx->individual_jacobians) {
         ctx->spec_pending = false;
         const std::string keep = ctx->last_error;
         if (spec_prepare(ctx) != FKS_OK) ctx->last_error = keep + (keep.empty() ? "" : "; ") + ctx->last_error;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
     }
-    const bool shaped = ctx->spec_fn && !tr && !small && !coop && !ctx->individual_jacobians;
+    /* (a path runs the generic path kernels: it neither builds nor launches the shape's module) */
+    const bool shaped = ctx->spec_fn && !path && !tr && !small && !coop && !ctx->individual_jacobians;
     /* a small batch runs the shape's small-batch kernel once the robot's module is built (it is
      * never built for a small batch: robots only ever simulated in small batches cost no compile) */
-    const bool shaped_small = small && ctx->spec_fn && ctx->spec_small_fn;
+    const bool shaped_small = !path && small && ctx->spec_fn && ctx->spec_small_fn;
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    ctx->last_kernel = tr ? FKS_KERNEL_TRACED
+    ctx->last_kernel = path ? (small ? FKS_KERNEL_PATH_SMALL_BATCH : FKS_KERNEL_PATH)
+                       : tr ? FKS_KERNEL_TRACED
                           : (shaped ? FKS_KERNEL_SHAPED
                                     : shaped_small ? FKS_KERNEL_SHAPED_SMALL_BATCH
                                     : (coop ? FKS_KERNEL_COOPERATIVE
@@ -1403,6 +1492,9 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     } else if (coop) {
         hipLaunchKernelGGL(coop_kernel_for(ctx->R.type), dim3((uint32_t)n), dim3(64 * ctx->coop_waves), ctx->coop_lds_bytes, s,
                            static_cast<const fksd::SimArgs*>(ctx->d_args));
+    } else if (path) {
+        hipLaunchKernelGGL(small ? path_small_kernel_for(ctx->R.type) : path_kernel_for(ctx->R.type, ctx->lean), dim3(grid),
+                           dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
     } else {
         hipLaunchKernelGGL(tr ? traced_kernel_for(ctx->R.type, ctx->lean)
                               : (small ? small_kernel_for(ctx->R.type) : kernel_for(ctx->R.type, ctx->individual_jacobians != 0, ctx->lean)),
@@ -1626,6 +1718,74 @@ fks_status fks_forward_simulate_mutable(fks_context* ctx, const double* starts, 
     if (n > 0 && !controller_state) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "null controller state");
     return simulate_host(ctx, starts, n, targets, num_targets, allow_contacts, out_positions, out_collided, out_microsteps,
                          out_resolver_iterations, out_error_flags, nullptr, controller_state);
+}
+
+/* what both path entries refuse before anything is staged or counted */
+static fks_status path_arguments(fks_context* ctx, uint64_t num_legs) {
+    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
+    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
+    if (num_legs == 0) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "a path needs at least one leg");
+    if (ctx->individual_jacobians)
+        return fail(ctx, FKS_ERR_UNSUPPORTED, "no path kernel with individual Jacobians (fks_set_individual_jacobians): chain plain calls");
+    return FKS_OK;
+}
+
+fks_status fks_forward_simulate_path_device(fks_context* ctx, const double* d_starts, uint64_t n, const double* d_waypoints,
+                                            uint64_t num_legs, uint64_t num_targets, uint64_t first_particle_id,
+                                            int32_t allow_contacts, double* d_out_positions, uint8_t* d_out_collided,
+                                            uint32_t* d_out_microsteps, uint32_t* d_out_resolver_iterations,
+                                            uint32_t* d_out_error_flags, void* stream, int32_t synchronize) {
+    const fks_status st = path_arguments(ctx, num_legs);
+    if (st != FKS_OK) return st;
+    return simulate_device(ctx, d_starts, n, d_waypoints, num_targets, first_particle_id, allow_contacts, d_out_positions,
+                           d_out_collided, d_out_microsteps, d_out_resolver_iterations, d_out_error_flags, stream, synchronize,
+                           nullptr, nullptr, num_legs);
+}
+
+fks_status fks_forward_simulate_path(fks_context* ctx, const double* starts, uint64_t n, const double* waypoints, uint64_t num_legs,
+                                     uint64_t num_targets, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
+                                     uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags) {
+    fks_status st = path_arguments(ctx, num_legs);
+    if (st != FKS_OK) return st;
+    if (n > 0 && (!starts || !waypoints || !out_positions)) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "null host buffer");
+    if (n > 0 && num_targets != 1 && num_targets != n)
+        return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "waypoints must hold 1 or n configurations per leg (SPCS:792)");
+    if (n > 0xffffffffull || num_legs >= (1ull << 31)) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "path too large");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = settle(ctx);
+    if (st != FKS_OK) return st;
+    if (n == 0)
+        return simulate_device(ctx, nullptr, 0, nullptr, 0, 0, allow_contacts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1,
+                               nullptr, nullptr, num_legs);
+    /* the staging buffers of the plain host calls, sized for the leg-major outputs */
+    const size_t W = (size_t)ctx->R.W;
+    const uint64_t rows = n * num_legs, nt = num_targets * num_legs;
+    if (rows > ctx->cap_particles) {
+        HIP_TRY(ctx, ensure(&ctx->d_starts, rows * W));
+        HIP_TRY(ctx, ensure(&ctx->d_out, rows * W));
+        HIP_TRY(ctx, ensure(&ctx->d_coll, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_micro, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_res, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_err, rows));
+        ctx->cap_particles = rows;
+    }
+    if (nt > ctx->cap_targets || !ctx->d_targets) {
+        HIP_TRY(ctx, ensure(&ctx->d_targets, nt * W));
+        ctx->cap_targets = nt;
+    }
+    HIP_TRY(ctx, hipMemcpy(ctx->d_starts, starts, n * W * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_targets, waypoints, nt * W * sizeof(double), hipMemcpyHostToDevice));
+    st = simulate_device(ctx, ctx->d_starts, n, ctx->d_targets, num_targets, 0, allow_contacts, ctx->d_out, ctx->d_coll, ctx->d_micro,
+                         ctx->d_res, ctx->d_err, nullptr, 1, nullptr, nullptr, num_legs);
+    if (st != FKS_OK) return st;
+    HIP_TRY(ctx, hipMemcpy(out_positions, ctx->d_out, rows * W * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_collided) HIP_TRY(ctx, hipMemcpy(out_collided, ctx->d_coll, rows, hipMemcpyDeviceToHost));
+    if (out_microsteps) HIP_TRY(ctx, hipMemcpy(out_microsteps, ctx->d_micro, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_resolver_iterations)
+        HIP_TRY(ctx, hipMemcpy(out_resolver_iterations, ctx->d_res, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_error_flags) HIP_TRY(ctx, hipMemcpy(out_error_flags, ctx->d_err, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
+    return FKS_OK;
 }
 
 }  // extern "C"

@@ -387,6 +387,15 @@ struct SimArgs {
     int32_t kin_mode;
     int32_t kin_pad;
     double* kin_out;
+    /* waypoint paths (fks_forward_simulate_path, the *_path kernels): the kernel's argument is
+     * an array of path_legs records, one per leg, equal except for what a leg owns: its RNG key
+     * (key0, key1), its targets, its start configurations (the caller's for leg 0, the previous
+     * leg's output slice afterwards) and its slices of the leg-major outputs (out_q ...
+     * out_err).  A particle's ticket space is path_legs x nseg segments: segment g is segment
+     * g % nseg of leg g / nseg, and seg_done counts g.  path_carry: the batch fits the
+     * resident waves, so a wave keeps its particle across every boundary */
+    uint32_t path_legs;
+    uint32_t path_carry;
 };
 
 enum {

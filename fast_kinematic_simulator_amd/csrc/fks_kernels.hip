@@ -3895,7 +3895,11 @@ __device__ __forceinline__ void kinematics(const SimArgs* __restrict__ args, dou
     }
 }
 
-template <int RT, bool TR, bool IND = false, bool LEAN = false, int COOP = 0>
+/* PATH: the waypoint-path kernels (fks_forward_simulate_path).  args is then an array of
+ * A.path_legs records, one per leg (SimArgs.path_legs), and a particle's ticket space is
+ * path_legs x nseg segments: a leg boundary is one more segment boundary, at which the
+ * particle is reset as the next call of a chain of plain calls would reset it */
+template <int RT, bool TR, bool IND = false, bool LEAN = false, int COOP = 0, bool PATH = false>
 __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ args, double* lds_mem) {
     const SimArgs& A = *args;
     const RobotDev& R = A.R;
@@ -3954,6 +3958,7 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
     unsigned long long* next_particle = reinterpret_cast<unsigned long long*>(s.lds() + LAY(*s.A).misc + 31);
     uint32_t* seg_seen = reinterpret_cast<uint32_t*>(s.lds() + LAY(*s.A).misc + 30);
     const uint32_t nseg = A.nseg;
+    const uint32_t nsegs = PATH ? nseg * A.path_legs : nseg; /* segments per particle (seg_done counts these) */
     uint64_t carry = kNoTicket; /* the next segment of the particle just run, claimed by this wave */
     bool carry_heavy = false;   /* ... and whether the segment just run was contact-heavy */
     /* call counters are summed per wave and flushed once when the queue is drained
@@ -3986,9 +3991,9 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
         } else {
             if (ln == 0) {
                 const uint64_t t = __hip_atomic_fetch_add(A.queue, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint64_t sg = (A.n > 0) ? t / A.n : (uint64_t)nseg;
+                const uint64_t sg = (A.n > 0) ? t / A.n : (uint64_t)nsegs;
                 uint32_t run = 1;
-                if (sg > 0 && sg < (uint64_t)nseg) {
+                if (sg > 0 && sg < (uint64_t)nsegs) {
                     uint32_t* done = A.seg_done + (t - sg * A.n);
                     uint32_t v = __hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     run = (v == (uint32_t)sg &&
@@ -4004,7 +4009,7 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             ticket = *next_particle;
             const uint32_t run = *seg_seen;
             wsync();
-            if ((A.n > 0 ? ticket / A.n : (uint64_t)nseg) >= (uint64_t)nseg) {
+            if ((A.n > 0 ? ticket / A.n : (uint64_t)nsegs) >= (uint64_t)nsegs) {
                 /* the queue is drained: this wave slot idles from here to the kernel's end */
                 const uint64_t bytes = wave_sum_u64(s.lane_bytes);
                 if (ln == 0) {
@@ -4043,8 +4048,19 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             else
                 __builtin_amdgcn_s_setprio(0);
         }
-        const uint64_t seg = ticket / A.n;
+        uint64_t seg = ticket / A.n;
         const uint64_t local = ticket - seg * A.n;
+        uint32_t leg = 0;
+        if constexpr (PATH) {
+            /* segment seg of the path is segment seg % nseg of leg seg / nseg (wave-uniform, so
+             * the leg's record is read with scalar loads like the plain kernels' only one) */
+            leg = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)seg / nseg));
+            seg -= (uint64_t)leg * nseg;
+        }
+        /* from here to the end of the segment A is the leg's record: its key, targets, start
+         * configurations and output slices (the plain kernels have one record) */
+        const SimArgs& A = PATH ? args[leg] : *args;
+        if constexpr (PATH) s.A = &A;
         const uint32_t step_begin = (uint32_t)seg * A.seg_steps;
         const uint32_t step_end = (seg + 1 == (uint64_t)nseg) ? A.T : step_begin + A.seg_steps;
         double* st = A.seg_state + local * (uint64_t)A.seg_stride; /* nseg > 1 only */
@@ -4061,6 +4077,14 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
         s.tcur_valid = false;
         if (ln == 0) s.selfref[RDIM(R, D)] = -1.0; /* no self-collision proof reference for this particle yet */
         const double* start = A.starts + local * (uint64_t)W;
+        /* a later leg starts where the leg before it ended: that leg's output slice, which
+         * another wave may have written */
+        auto start_at = [&](int i) -> double {
+            if constexpr (PATH) {
+                if (leg > 0) return load_coherent(start + i);
+            }
+            return start[i];
+        };
         const double* target = (A.num_targets == A.n) ? A.targets + local * (uint64_t)W : A.targets;
         bool collided = false;
         bool any_failed = false;
@@ -4074,13 +4098,17 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             if constexpr (RT == FKS_ROBOT_LINKED) {
                 if (ln < D) {
                     const JointDev& jd = s.joints()[s.dofj()[ln]];
-                    cfg[ln] = (jd.type == FKS_JOINT_CONTINUOUS) ? fks_math::wrap_revolute(start[ln])
-                                                                : clamp(start[ln], jd.lo, jd.hi);
+                    cfg[ln] = (jd.type == FKS_JOINT_CONTINUOUS) ? fks_math::wrap_revolute(start_at(ln))
+                                                                : clamp(start_at(ln), jd.lo, jd.hi);
                 }
             } else if constexpr (RT == FKS_ROBOT_SE2) {
-                if (ln < 3) cfg[ln] = (ln == 2) ? fks_math::wrap_revolute(start[2]) : start[ln];
+                if (ln < 3) cfg[ln] = (ln == 2) ? fks_math::wrap_revolute(start_at(2)) : start_at(ln);
             } else {
-                if (ln < 12) cfg[ln] = start[ln];
+                if (ln < 12) cfg[ln] = start_at(ln);
+            }
+            if constexpr (PATH) {
+                /* the chain's next call would start without round proofs of the call before */
+                if (leg > 0 && ln < RDIM(R, nrounds)) s.rstate[kRoundState * ln + 12] = kInvalidRound;
             }
         } else {
             /* resume: configuration from out_q, controller state and per-particle totals
@@ -4202,20 +4230,30 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             s.phase()[FKS_PHASE_OUTPUT] += t_end - t_out;
             s.phase()[FKS_PHASE_PARTICLE] += t_end;
         }
-        if (nseg > 1) {
+        if (nsegs > 1) {
+            /* the particle's next segment in seg_done's count: the next of this leg, or the
+             * first of the next leg when this one has ended (the tickets of the segments
+             * skipped find seg_done past them) */
+            uint64_t next_seg = seg + 1;
+            if constexpr (PATH) next_seg = (uint64_t)leg * nseg + (ended ? (uint64_t)nseg : seg + 1);
             /* publish the resting state; if the next segment's ticket is already out, claim
              * the segment and run it here (its holder, if it looked earlier, skipped it) */
             publish_fence(); /* every lane's state stores have completed */
             wsync();
             if (ln == 0) {
                 uint32_t nv = ended ? nseg : (uint32_t)seg + 1u;
+                bool more = !ended; /* the particle has a further segment */
+                if constexpr (PATH) {
+                    nv = (uint32_t)next_seg;
+                    more = nv < nsegs;
+                }
                 __hip_atomic_store(A.seg_done + local, nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 publish_fence(); /* the store is visible before the ticket counter is read (Dekker with the holder) */
                 uint32_t cont = 0;
                 /* a contact-heavy segment (many resolver iterations) keeps its wave: the
                  * particle's next segment is claimed at once instead of waiting for its
                  * ticket, so the longest particles are not paced by the round-robin */
-                bool heavy = !ended && A.seg_heavy_resolver != 0 && s.resolver_count >= A.seg_heavy_resolver;
+                bool heavy = more && A.seg_heavy_resolver != 0 && s.resolver_count >= A.seg_heavy_resolver;
                 if (A.seg_heavy_rel) {
                     /* relative to the batch: in a contact-heavy batch (its mean so far at or above
                      * the absolute threshold: most segments resolve contacts) only the outliers
@@ -4237,8 +4275,12 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
                         *pend = mine;
                     }
                 }
-                if (!ended) {
-                    const uint64_t next_ticket = (seg + 1) * A.n + local;
+                if constexpr (PATH) {
+                    /* every particle has a wave (SimArgs.path_carry): it keeps it across legs */
+                    if (more && A.path_carry) heavy = true;
+                }
+                if (more) {
+                    const uint64_t next_ticket = next_seg * A.n + local;
                     const uint64_t issued =
                         heavy ? ~0ull : __hip_atomic_load(A.queue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (issued > next_ticket &&
@@ -4251,7 +4293,7 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             wsync();
             const uint32_t cont = *seg_seen;
             if (cont) {
-                carry = (seg + 1) * A.n + local;
+                carry = next_seg * A.n + local;
                 carry_heavy = cont == 2u;
             }
         }
@@ -4381,6 +4423,38 @@ extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_indiv(const
 extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_traced(const SimArgs* __restrict__ args) {
     extern __shared__ __attribute__((aligned(16))) double lds_mem[];
     simulate_particles<FKS_ROBOT_LINKED, true, false, true>(args, lds_mem);
+}
+
+/* waypoint paths (fks_forward_simulate_path): PATH instantiations at the throughput budget ... */
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_path(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_path(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, true, 0, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_path(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_path(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true>(args, lds_mem);
+}
+/* ... and at the small-batch budget, for paths whose batch fits its resident waves: the wave
+ * carries its particle through every leg (SimArgs.path_carry) */
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_linked_path_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_path_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_path_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true>(args, lds_mem);
 }
 
 extern "C" __global__ void FKS_KERNEL_ATTRS fks_check_configs_linked(const SimArgs* __restrict__ args) {

@@ -211,9 +211,11 @@ fks_status fks_multi_set_robot(fks_multi_context* m, const fks_robot_desc* robot
     return FKS_OK;
 }
 
-fks_status fks_multi_forward_simulate(fks_multi_context* m, const double* starts, uint64_t n, const double* targets,
-                                      uint64_t num_targets, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
-                                      uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags) {
+/* fks_multi_forward_simulate (legs == 0) and fks_multi_forward_simulate_path (legs >= 1: targets
+ * holds the waypoints [legs][num_targets][W], the outputs are leg-major [legs][n]...) */
+static fks_status multi_simulate(fks_multi_context* m, const double* starts, uint64_t n, const double* targets, uint64_t legs,
+                                 uint64_t num_targets, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
+                                 uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags) {
     if (!m) return FKS_ERR_INVALID_ARGUMENT;
     if (m->width <= 0) return mfail(m, FKS_ERR_NO_ROBOT, "fks_multi_set_robot has not been called");
     if (n > 0 && (!starts || !targets || !out_positions)) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "null host buffer");
@@ -221,7 +223,10 @@ fks_status fks_multi_forward_simulate(fks_multi_context* m, const double* starts
     const auto t0 = std::chrono::steady_clock::now();
     const size_t W = (size_t)m->width;
     const int32_t ndev = active_count(m);
-    const uint64_t call = m->call_index++;
+    const bool path = legs > 0;
+    const uint64_t K = path ? legs : 1; /* output slices per particle */
+    const uint64_t call = m->call_index;
+    m->call_index += K;
     /* one host thread per device: stage in, launch, stage out (the devices run concurrently) */
     on_device_threads(ndev, [&](int32_t g) {
         auto& d = m->devices[(size_t)g];
@@ -233,54 +238,65 @@ fks_status fks_multi_forward_simulate(fks_multi_context* m, const double* starts
         const uint64_t k = hi - lo;
         DCTX(d, fks_set_call_index(d.ctx, call), "fks_set_call_index");
         DHIP(d, hipSetDevice(d.device));
-        if (k > d.cap) {
-            DHIP(d, grow(&d.d_starts, k * W));
-            DHIP(d, grow(&d.d_out, k * W));
-            DHIP(d, grow(&d.d_coll, k));
-            DHIP(d, grow(&d.d_micro, k));
-            DHIP(d, grow(&d.d_res, k));
-            DHIP(d, grow(&d.d_err, k));
-            d.cap = k;
+        const uint64_t rows = k * K; /* the shard's output rows: a path's are leg-major [K][k] */
+        if (rows > d.cap) {
+            DHIP(d, grow(&d.d_starts, rows * W));
+            DHIP(d, grow(&d.d_out, rows * W));
+            DHIP(d, grow(&d.d_coll, rows));
+            DHIP(d, grow(&d.d_micro, rows));
+            DHIP(d, grow(&d.d_res, rows));
+            DHIP(d, grow(&d.d_err, rows));
+            d.cap = rows;
         }
-        const uint64_t nt = (num_targets == n) ? k : 1;
-        if (nt > d.cap_targets) {
-            DHIP(d, grow(&d.d_targets, nt * W));
-            d.cap_targets = nt;
+        const uint64_t nt = (num_targets == n) ? k : 1; /* per leg */
+        if (nt * K > d.cap_targets) {
+            DHIP(d, grow(&d.d_targets, nt * K * W));
+            d.cap_targets = nt * K;
         }
         if (k == 0) {
             DCTX(d, fks_get_last_call_counters(d.ctx, &d.counters), "fks_get_last_call_counters"); /* settles */
             std::memset(&d.counters, 0, sizeof(d.counters));
             return;
         }
-        const size_t in_bytes = (k + nt) * W * sizeof(double);
-        const size_t out_bytes = k * W * sizeof(double) + k * (1 + 3 * sizeof(uint32_t));
+        const size_t in_bytes = (k + nt * K) * W * sizeof(double);
+        const size_t out_bytes = rows * W * sizeof(double) + rows * (1 + 3 * sizeof(uint32_t));
         DHIP(d, grow_pinned(&d.h_in, &d.cap_h_in, in_bytes));
         DHIP(d, grow_pinned(&d.h_out, &d.cap_h_out, out_bytes));
         double* h_starts = reinterpret_cast<double*>(d.h_in);
         double* h_targets = h_starts + k * W;
         std::memcpy(h_starts, starts + lo * W, k * W * sizeof(double));
-        std::memcpy(h_targets, targets + (num_targets == n ? lo * W : 0), nt * W * sizeof(double));
+        for (uint64_t leg = 0; leg < K; ++leg) /* the shard's rows of every leg's targets */
+            std::memcpy(h_targets + leg * nt * W, targets + (leg * num_targets + (num_targets == n ? lo : 0)) * W,
+                        nt * W * sizeof(double));
         DHIP(d, hipMemcpyAsync(d.d_starts, h_starts, k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
-        DHIP(d, hipMemcpyAsync(d.d_targets, h_targets, nt * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
-        DCTX(d, fks_forward_simulate_device(d.ctx, d.d_starts, k, d.d_targets, nt, lo, allow_contacts, d.d_out, d.d_coll, d.d_micro,
-                                            d.d_res, d.d_err, d.stream, 0),
-             "fks_forward_simulate_device");
+        DHIP(d, hipMemcpyAsync(d.d_targets, h_targets, nt * K * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
+        if (path)
+            DCTX(d, fks_forward_simulate_path_device(d.ctx, d.d_starts, k, d.d_targets, legs, nt, lo, allow_contacts, d.d_out, d.d_coll,
+                                                     d.d_micro, d.d_res, d.d_err, d.stream, 0),
+                 "fks_forward_simulate_path_device");
+        else
+            DCTX(d, fks_forward_simulate_device(d.ctx, d.d_starts, k, d.d_targets, nt, lo, allow_contacts, d.d_out, d.d_coll, d.d_micro,
+                                                d.d_res, d.d_err, d.stream, 0),
+                 "fks_forward_simulate_device");
         double* h_q = reinterpret_cast<double*>(d.h_out);
-        uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + k * W);
-        uint32_t* h_res = h_micro + k;
-        uint32_t* h_err = h_res + k;
-        uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + k);
-        DHIP(d, hipMemcpyAsync(h_q, d.d_out, k * W * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_micro, d.d_micro, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_res, d.d_res, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_err, d.d_err, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_coll, d.d_coll, k, hipMemcpyDeviceToHost, d.stream));
+        uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + rows * W);
+        uint32_t* h_res = h_micro + rows;
+        uint32_t* h_err = h_res + rows;
+        uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + rows);
+        DHIP(d, hipMemcpyAsync(h_q, d.d_out, rows * W * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_micro, d.d_micro, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_res, d.d_res, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_err, d.d_err, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_coll, d.d_coll, rows, hipMemcpyDeviceToHost, d.stream));
         DHIP(d, hipStreamSynchronize(d.stream));
-        std::memcpy(out_positions + lo * W, h_q, k * W * sizeof(double));
-        if (out_collided) std::memcpy(out_collided + lo, h_coll, k);
-        if (out_microsteps) std::memcpy(out_microsteps + lo, h_micro, k * sizeof(uint32_t));
-        if (out_resolver_iterations) std::memcpy(out_resolver_iterations + lo, h_res, k * sizeof(uint32_t));
-        if (out_error_flags) std::memcpy(out_error_flags + lo, h_err, k * sizeof(uint32_t));
+        for (uint64_t leg = 0; leg < K; ++leg) {
+            const uint64_t src = leg * k, dst = leg * n + lo;
+            std::memcpy(out_positions + dst * W, h_q + src * W, k * W * sizeof(double));
+            if (out_collided) std::memcpy(out_collided + dst, h_coll + src, k);
+            if (out_microsteps) std::memcpy(out_microsteps + dst, h_micro + src, k * sizeof(uint32_t));
+            if (out_resolver_iterations) std::memcpy(out_resolver_iterations + dst, h_res + src, k * sizeof(uint32_t));
+            if (out_error_flags) std::memcpy(out_error_flags + dst, h_err + src, k * sizeof(uint32_t));
+        }
         DCTX(d, fks_get_last_call_counters(d.ctx, &d.counters), "fks_get_last_call_counters"); /* settles the launch */
     });
     const fks_status st = collect_status(m, ndev);
@@ -302,6 +318,23 @@ fks_status fks_multi_forward_simulate(fks_multi_context* m, const double* starts
     m->last.calls = 1;
     m->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return FKS_OK;
+}
+
+fks_status fks_multi_forward_simulate(fks_multi_context* m, const double* starts, uint64_t n, const double* targets,
+                                      uint64_t num_targets, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
+                                      uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags) {
+    return multi_simulate(m, starts, n, targets, 0, num_targets, allow_contacts, out_positions, out_collided, out_microsteps,
+                          out_resolver_iterations, out_error_flags);
+}
+
+fks_status fks_multi_forward_simulate_path(fks_multi_context* m, const double* starts, uint64_t n, const double* waypoints,
+                                           uint64_t num_legs, uint64_t num_targets, int32_t allow_contacts, double* out_positions,
+                                           uint8_t* out_collided, uint32_t* out_microsteps, uint32_t* out_resolver_iterations,
+                                           uint32_t* out_error_flags) {
+    if (!m) return FKS_ERR_INVALID_ARGUMENT;
+    if (num_legs == 0) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "a path needs at least one leg");
+    return multi_simulate(m, starts, n, waypoints, num_legs, num_targets, allow_contacts, out_positions, out_collided,
+                          out_microsteps, out_resolver_iterations, out_error_flags);
 }
 
 fks_status fks_multi_set_active_devices(fks_multi_context* m, int32_t count) {

@@ -248,6 +248,30 @@ class HipParticleContactSimulator:
         return {"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
                 "error_flags": errors}
 
+    def forward_simulate_path_arrays(self, robot: RobotDescription, start_positions, waypoints, allow_contacts: bool) -> dict:
+        """A batch along a waypoint path in one launch (fks_forward_simulate_path): starts (n, W),
+        waypoints (K, 1 or n, W) -- a (K, W) array is one shared waypoint per leg.  Returns
+        [K, n, ...] arrays: leg k is what forward_simulate_arrays returns from leg k-1's positions
+        toward waypoints[k] at call index get_call_index() + k, byte for byte; the call index
+        advances by K."""
+        self.set_robot(robot)
+        W = robot.config_width
+        starts = np.ascontiguousarray(np.asarray(start_positions, dtype=np.float64).reshape(-1, W))
+        n = starts.shape[0]
+        way, K, nt = _path_waypoints(waypoints, W, n)
+        out = np.zeros((K, n, W), dtype=np.float64)
+        collided = np.zeros((K, n), dtype=np.uint8)
+        micro = np.zeros((K, n), dtype=np.uint32)
+        resolver = np.zeros((K, n), dtype=np.uint32)
+        errors = np.zeros((K, n), dtype=np.uint32)
+        st = self._lib.fks_forward_simulate_path(
+            self._ctx, _capi.as_ptr(starts, ctypes.c_double), n, _capi.as_ptr(way, ctypes.c_double), K, nt,
+            1 if allow_contacts else 0, _capi.as_ptr(out, ctypes.c_double), _capi.as_ptr(collided, ctypes.c_uint8),
+            _capi.as_ptr(micro, ctypes.c_uint32), _capi.as_ptr(resolver, ctypes.c_uint32), _capi.as_ptr(errors, ctypes.c_uint32))
+        _capi.check(st, self._ctx, "fks_forward_simulate_path")
+        return {"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
+                "error_flags": errors}
+
     def forward_simulate_mutable_arrays(self, robot: RobotDescription, start_positions, target_positions, allow_contacts: bool,
                                         controller_state) -> dict:
         """ForwardSimulateMutableRobot (SPCS:843-919) for a batch (fks_forward_simulate_mutable):
@@ -492,6 +516,34 @@ class HipParticleContactSimulator:
             ctypes.c_void_p(d_out_error_flags or None), ctypes.c_void_p(stream or None), 1 if synchronize else 0)
         _capi.check(st, self._ctx, "fks_forward_simulate_device")
 
+    def forward_simulate_path_device(self, robot: RobotDescription, d_starts, n: int, d_waypoints, num_legs: int, num_targets: int,
+                                     first_particle_id: int, allow_contacts: bool, d_out_positions, d_out_collided=0,
+                                     d_out_microsteps=0, d_out_resolver_iterations=0, d_out_error_flags=0, stream=0,
+                                     synchronize=False):
+        """fks_forward_simulate_path_device: device pointers (int) as in forward_simulate_device;
+        d_waypoints [num_legs][num_targets][W], the outputs leg-major ([num_legs][n]...)."""
+        self.set_robot(robot)
+        st = self._lib.fks_forward_simulate_path_device(
+            self._ctx, ctypes.c_void_p(d_starts), n, ctypes.c_void_p(d_waypoints), num_legs, num_targets, first_particle_id,
+            1 if allow_contacts else 0, ctypes.c_void_p(d_out_positions), ctypes.c_void_p(d_out_collided or None),
+            ctypes.c_void_p(d_out_microsteps or None), ctypes.c_void_p(d_out_resolver_iterations or None),
+            ctypes.c_void_p(d_out_error_flags or None), ctypes.c_void_p(stream or None), 1 if synchronize else 0)
+        _capi.check(st, self._ctx, "fks_forward_simulate_path_device")
+
+
+def _path_waypoints(waypoints, W: int, n: int):
+    """The waypoints of a path as a contiguous (K, 1 or n, W) array, with K and the per-leg count."""
+    way = np.asarray(waypoints, dtype=np.float64)
+    if way.ndim == 2 and way.shape[0] > 0:
+        way = way[:, None, :]
+    if way.size == 0:
+        way = way.reshape(0, 1, W)
+    if way.ndim != 3 or way.shape[2] != W:
+        raise ValueError("waypoints must be (legs, 1 or n, W), or (legs, W) for one shared waypoint per leg")
+    if n > 0 and way.shape[1] not in (1, n):
+        raise ValueError("every leg must hold 1 or len(start_positions) waypoints (SPCS:792)")
+    return np.ascontiguousarray(way), int(way.shape[0]), int(way.shape[1])
+
 
 class MultiDeviceSimulator:
     """One process, several MI355X devices (fks_create_multi): every batch is split into
@@ -574,6 +626,27 @@ class MultiDeviceSimulator:
             1 if allow_contacts else 0, _capi.as_ptr(out, ctypes.c_double), _capi.as_ptr(collided, ctypes.c_uint8),
             _capi.as_ptr(micro, ctypes.c_uint32), _capi.as_ptr(resolver, ctypes.c_uint32), _capi.as_ptr(errors, ctypes.c_uint32))
         self._check(st, "fks_multi_forward_simulate")
+        return {"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
+                "error_flags": errors}
+
+    def forward_simulate_path_arrays(self, robot: RobotDescription, start_positions, waypoints, allow_contacts: bool) -> dict:
+        """fks_multi_forward_simulate_path: HipParticleContactSimulator.forward_simulate_path_arrays
+        sharded over the devices (bit-identical to one device)."""
+        self.set_robot(robot)
+        W = robot.config_width
+        starts = np.ascontiguousarray(np.asarray(start_positions, dtype=np.float64).reshape(-1, W))
+        n = starts.shape[0]
+        way, K, nt = _path_waypoints(waypoints, W, n)
+        out = np.zeros((K, n, W), dtype=np.float64)
+        collided = np.zeros((K, n), dtype=np.uint8)
+        micro = np.zeros((K, n), dtype=np.uint32)
+        resolver = np.zeros((K, n), dtype=np.uint32)
+        errors = np.zeros((K, n), dtype=np.uint32)
+        st = self._lib.fks_multi_forward_simulate_path(
+            self._ctx, _capi.as_ptr(starts, ctypes.c_double), n, _capi.as_ptr(way, ctypes.c_double), K, nt,
+            1 if allow_contacts else 0, _capi.as_ptr(out, ctypes.c_double), _capi.as_ptr(collided, ctypes.c_uint8),
+            _capi.as_ptr(micro, ctypes.c_uint32), _capi.as_ptr(resolver, ctypes.c_uint32), _capi.as_ptr(errors, ctypes.c_uint32))
+        self._check(st, "fks_multi_forward_simulate_path")
         return {"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
                 "error_flags": errors}
 

@@ -151,6 +151,29 @@ class DeviceSet {
               ctx_, what);
     }
 
+    /* a batch along a waypoint path in one launch per device; the arguments are those of
+     * fks_forward_simulate_path (leg-major outputs), the devices chosen as for simulate() */
+    void simulate_path(const double* starts, uint64_t n, const double* waypoints, uint64_t num_legs, uint64_t num_targets,
+                       bool allow_contacts, double* out_positions, uint8_t* out_collided, uint32_t* out_microsteps,
+                       uint32_t* out_resolver_iterations, uint32_t* out_error_flags, const char* what) {
+        last_devices_ = devices_for(n);
+        if (last_devices_ >= 2) {
+            /* every device uses the call indices devices[0] would have used */
+            const uint64_t call = fks_get_call_index(ctx_);
+            MultiCheck(fks_multi_set_active_devices(multi_.get(), last_devices_), what);
+            MultiCheck(fks_multi_set_call_index(multi_.get(), call), what);
+            MultiCheck(fks_multi_forward_simulate_path(multi_.get(), starts, n, waypoints, num_legs, num_targets, allow_contacts ? 1 : 0,
+                                                       out_positions, out_collided, out_microsteps, out_resolver_iterations,
+                                                       out_error_flags),
+                       what);
+            Check(fks_set_call_index(ctx_, call + num_legs), ctx_, what);
+            return;
+        }
+        Check(fks_forward_simulate_path(ctx_, starts, n, waypoints, num_legs, num_targets, allow_contacts ? 1 : 0, out_positions,
+                                        out_collided, out_microsteps, out_resolver_iterations, out_error_flags),
+              ctx_, what);
+    }
+
     /* batched CheckConfigCollision (SPCS:1398-1416) */
     void check_configs(const double* configs, uint64_t n, double inflation_ratio, uint8_t* out_collided, uint32_t* out_error_flags,
                        const char* what) const {

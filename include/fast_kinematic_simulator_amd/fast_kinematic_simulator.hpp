@@ -246,6 +246,48 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
         (void)display_fn;
         return Batch(Derived(immutable_robot), start_positions, target_positions, allow_contacts, fks_reverse_simulate);
     }
+    /* Not part of SimulatorInterface: the batch along a waypoint path in one launch
+     * (fks_forward_simulate_path), for the planner's edge-after-edge loops.  waypoints[k] holds 1
+     * or start_positions.size() configurations, the same count for every leg; results[k][i] is
+     * what the k-th of waypoints.size() chained ForwardSimulateRobots calls returns for particle
+     * i, each starting from the result_configs of the one before, bit for bit. */
+    std::vector<std::vector<SimulationResult>> ForwardSimulateRobotsAlongPath(
+        const std::shared_ptr<BaseRobotType>& immutable_robot, const std::vector<Configuration, ConfigAlloc>& start_positions,
+        const std::vector<std::vector<Configuration, ConfigAlloc>>& waypoints, const bool allow_contacts) {
+        if (waypoints.empty()) throw std::invalid_argument("a path needs at least one leg");
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        const size_t K = waypoints.size(), n = start_positions.size(), nt = waypoints[0].size();
+        if (n > 0 && nt != 1 && nt != n) throw std::invalid_argument("every leg must hold 1 or start_positions.size() waypoints (SPCS:792)");
+        SetRobot(robot);
+        std::vector<double> s, t;
+        for (const auto& c : start_positions) {
+            const std::vector<double> f = robot.ToFlat(c);
+            s.insert(s.end(), f.begin(), f.end());
+        }
+        for (const auto& leg : waypoints) {
+            if (leg.size() != nt) throw std::invalid_argument("every leg must hold the same number of waypoints");
+            for (const auto& c : leg) {
+                const std::vector<double> f = robot.ToFlat(c);
+                t.insert(t.end(), f.begin(), f.end());
+            }
+        }
+        const size_t W = n ? s.size() / n : 0;
+        std::vector<double> q(K * n * W);
+        std::vector<uint8_t> collided(K * n);
+        last_micro_.assign(K * n, 0);
+        last_resolver_.assign(K * n, 0);
+        last_errors_.assign(K * n, 0);
+        dev_->simulate_path(s.data(), n, t.data(), K, nt, allow_contacts, q.data(), collided.data(), last_micro_.data(),
+                            last_resolver_.data(), last_errors_.data(), "ForwardSimulateRobotsAlongPath");
+        std::vector<std::vector<SimulationResult>> out(K);
+        for (size_t k = 0; k < K; ++k) {
+            out[k].reserve(n);
+            for (size_t i = 0; i < n; ++i)
+                out[k].emplace_back(robot.FromFlat(q.data() + (k * n + i) * W), nt == n ? waypoints[k][i] : waypoints[k][0],
+                                    collided[k * n + i] != 0, true);
+        }
+        return out;
+    }
     /* SPCS:824-829: a clone reset to the start (controllers zeroed) */
     SimulationResult ForwardSimulateRobot(const std::shared_ptr<BaseRobotType>& immutable_robot, const Configuration& start_position,
                                           const Configuration& target_position, const bool allow_contacts,

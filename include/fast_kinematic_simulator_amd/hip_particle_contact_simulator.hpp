@@ -357,6 +357,52 @@ class HipParticleContactSimulator {
         (void)display_fn;
         return Simulate(immutable_robot, start_positions, target_positions, allow_contacts, false);
     }
+    /* The batch along a waypoint path in one launch (fks_forward_simulate_path; no reference
+     * counterpart: the planner's edge-after-edge loop over ForwardSimulateRobots).  waypoints[k]
+     * holds 1 or start_positions.size() configurations, the same count for every leg.
+     * results[k][i] is what the k-th of waypoints.size() chained ForwardSimulateRobots calls
+     * returns for particle i, each starting from the result_configs of the one before, bit for
+     * bit; a particle starts its next leg when its own leg ends. */
+    std::vector<std::vector<SimulationResult>> ForwardSimulateRobotsAlongPath(const RobotDescription& immutable_robot,
+                                                                              const std::vector<Configuration>& start_positions,
+                                                                              const std::vector<std::vector<Configuration>>& waypoints,
+                                                                              bool allow_contacts) {
+        if (waypoints.empty()) throw std::invalid_argument("a path needs at least one leg");
+        const size_t K = waypoints.size(), n = start_positions.size(), nt = waypoints[0].size();
+        if (n > 0 && nt != 1 && nt != n) throw std::invalid_argument("every leg must hold 1 or start_positions.size() waypoints");
+        SetRobot(immutable_robot);
+        const size_t W = (size_t)immutable_robot.ConfigurationWidth();
+        std::vector<double> s(n * W), t(K * nt * W), out(K * n * W);
+        for (size_t i = 0; i < n; ++i) {
+            if (start_positions[i].size() != W) throw std::invalid_argument("start configuration has the wrong width");
+            std::copy(start_positions[i].begin(), start_positions[i].end(), s.begin() + i * W);
+        }
+        for (size_t k = 0; k < K; ++k) {
+            if (waypoints[k].size() != nt) throw std::invalid_argument("every leg must hold the same number of waypoints");
+            for (size_t i = 0; i < nt; ++i) {
+                if (waypoints[k][i].size() != W) throw std::invalid_argument("waypoint configuration has the wrong width");
+                std::copy(waypoints[k][i].begin(), waypoints[k][i].end(), t.begin() + (k * nt + i) * W);
+            }
+        }
+        std::vector<uint8_t> collided(K * n);
+        std::vector<uint32_t> micro(K * n), resolver(K * n), errors(K * n);
+        dev_.simulate_path(s.data(), n, t.data(), K, nt, allow_contacts, out.data(), collided.data(), micro.data(), resolver.data(),
+                           errors.data(), "ForwardSimulateRobotsAlongPath");
+        std::vector<std::vector<SimulationResult>> results(K, std::vector<SimulationResult>(n));
+        for (size_t k = 0; k < K; ++k)
+            for (size_t i = 0; i < n; ++i) {
+                SimulationResult& r = results[k][i];
+                const size_t row = k * n + i;
+                r.result_config.assign(out.begin() + row * W, out.begin() + (row + 1) * W);
+                r.target_config = nt == n ? waypoints[k][i] : waypoints[k][0];
+                r.did_contact = collided[row] != 0;
+                r.outcome_is_valid = true;
+                r.microsteps = micro[row];
+                r.resolver_iterations = resolver[row];
+                r.error_flags = errors[row];
+            }
+        return results;
+    }
     /* ReverseSimulateRobots (SPCS:806-822) == forward simulation (SPCS:838-841) */
     std::vector<SimulationResult> ReverseSimulateRobots(const RobotDescription& immutable_robot,
                                                         const std::vector<Configuration>& start_positions,

@@ -17,6 +17,8 @@
  *   fks_forward_simulate       -> SimpleParticleContactSimulator::ForwardSimulateRobots (SPCS:788-804)
  *   fks_reverse_simulate       -> SimpleParticleContactSimulator::ReverseSimulateRobots (SPCS:806-822)
  *   fks_forward_simulate_device-> same as fks_forward_simulate, inputs/outputs already in HBM
+ *   fks_forward_simulate_path  -> the planner's loop of ForwardSimulateRobots calls over a waypoint list
+ *                                 (no single reference function), in one launch
  *   fks_check_config_collision -> SimpleParticleContactSimulator::CheckConfigCollision   (SPCS:1398-1416),
  *                                 batched (one call per configuration in the reference)
  *   fks_get_statistics         -> SimpleParticleContactSimulator::GetStatistics          (SPCS:488-500)
@@ -314,6 +316,41 @@ fks_status fks_forward_simulate_device(fks_context* ctx, const double* d_starts,
                                        uint32_t* d_out_error_flags, void* stream,
                                        int32_t synchronize);
 
+/* A batch along a waypoint path in one launch (added within ABI 10).  With the context at call
+ * index c, the call returns byte for byte what this chain of plain calls returns, and
+ * leaves the call index at c + num_legs:
+ *     q_0 = starts
+ *     leg k = 0 .. num_legs-1:  fks_set_call_index(c + k);
+ *                               r_k = fks_forward_simulate(q_k, waypoints[k], allow_contacts);
+ *                               q_{k+1} = r_k positions
+ * so every leg begins with ResetPosition(q_k) (controllers zeroed, joint limits / angle wrap
+ * applied again), its collided flag, counts and error bits are its own, and a leg that ends
+ * early (failed resolve, contact with allow_contacts == 0, shortcut distance, error bit)
+ * hands the configuration it returned to the next leg.  A particle starts leg k+1 when its
+ * own leg k ends: no leg waits for the batch.
+ * waypoints: [num_legs][num_targets][W] doubles, num_targets == 1 or n for every leg.
+ * Outputs are leg-major: out_positions [num_legs][n][W] (required: leg k's slice is leg
+ * k+1's start), the other four [num_legs][n] (each may be NULL).
+ * fks_get_statistics and the work counters of fks_get_last_call_counters grow by the chain's
+ * sums; `calls` counts 1.  num_legs == 0, or more legs than the segment counter holds
+ * (num_legs x segments per leg < 2^31), is FKS_ERR_INVALID_ARGUMENT; n == 0 succeeds and
+ * consumes num_legs call indices.  A context with fks_set_individual_jacobians on returns
+ * FKS_ERR_UNSUPPORTED.  fks_set_segment_steps / _policy / _heavy_relative and
+ * fks_set_small_batch_kernel apply as to a plain call (fks_set_cooperative_waves does not);
+ * the call runs the generic path kernels (FKS_KERNEL_PATH / FKS_KERNEL_PATH_SMALL_BATCH) and
+ * never builds or launches the shape-specialised module. */
+fks_status fks_forward_simulate_path(fks_context* ctx, const double* starts, uint64_t n, const double* waypoints,
+                                     uint64_t num_legs, uint64_t num_targets, int32_t allow_contacts,
+                                     double* out_positions, uint8_t* out_collided, uint32_t* out_microsteps,
+                                     uint32_t* out_resolver_iterations, uint32_t* out_error_flags);
+/* Same with device buffers (see fks_forward_simulate_device): rows [a, b) of a path with
+ * first_particle_id = a equal the same rows of the whole path. */
+fks_status fks_forward_simulate_path_device(fks_context* ctx, const double* d_starts, uint64_t n, const double* d_waypoints,
+                                            uint64_t num_legs, uint64_t num_targets, uint64_t first_particle_id,
+                                            int32_t allow_contacts, double* d_out_positions, uint8_t* d_out_collided,
+                                            uint32_t* d_out_microsteps, uint32_t* d_out_resolver_iterations,
+                                            uint32_t* d_out_error_flags, void* stream, int32_t synchronize);
+
 /* CheckConfigCollision (SPCS:1398-1416) for a batch of n configurations (host
  * buffers): SetPosition(config), CheckEnvironmentCollision at threshold
  * inflation_ratio * res (SPCS:1403, 921-981) and CheckSelfCollisions at extended
@@ -449,8 +486,11 @@ typedef enum {
     FKS_KERNEL_TRACED = 4,       /* fks_simulate_<family>[_lean]_traced */
     FKS_KERNEL_INDIVIDUAL = 5,   /* fks_simulate_<family>[_lean]_indiv (fks_set_individual_jacobians) */
     FKS_KERNEL_COOPERATIVE = 6,  /* ABI 10: fks_simulate_<family>_coop (fks_set_cooperative_waves) */
-    FKS_KERNEL_SHAPED_SMALL_BATCH = 7 /* ABI 10: the shape-specialised module's small-batch kernel
-                                         (a small batch once the robot's module is built) */
+    FKS_KERNEL_SHAPED_SMALL_BATCH = 7, /* ABI 10: the shape-specialised module's small-batch kernel
+                                          (a small batch once the robot's module is built) */
+    FKS_KERNEL_PATH = 8,             /* fks_simulate_<family>[_lean]_path (fks_forward_simulate_path) */
+    FKS_KERNEL_PATH_SMALL_BATCH = 9  /* fks_simulate_<family>_path_small: a path whose batch fits the
+                                        small-batch kernel's resident waves */
 } fks_kernel_kind;
 /* The launch layout fks_set_robot chose (ABI 8; diagnostic, no reference counterpart). */
 typedef struct fks_launch_info {
@@ -681,6 +721,12 @@ int32_t fks_multi_active_devices(const fks_multi_context* m);
 fks_status fks_multi_forward_simulate(fks_multi_context* m, const double* starts, uint64_t n, const double* targets,
                                       uint64_t num_targets, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
                                       uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags);
+/* fks_forward_simulate_path over the active devices: the same contiguous shards, every shard at
+ * the multi context's call index, which then advances by num_legs */
+fks_status fks_multi_forward_simulate_path(fks_multi_context* m, const double* starts, uint64_t n, const double* waypoints,
+                                           uint64_t num_legs, uint64_t num_targets, int32_t allow_contacts, double* out_positions,
+                                           uint8_t* out_collided, uint32_t* out_microsteps, uint32_t* out_resolver_iterations,
+                                           uint32_t* out_error_flags);
 fks_status fks_multi_get_statistics(const fks_multi_context* m, fks_statistics* out);
 fks_status fks_multi_reset_statistics(fks_multi_context* m);
 fks_status fks_multi_get_last_call_counters(const fks_multi_context* m, fks_call_counters* out);
