@@ -52,6 +52,13 @@ extern "C" __global__ void fks_simulate_se3_path(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_linked_path_small(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_se2_path_small(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_se3_path_small(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_jobs(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_lean_jobs(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se2_jobs(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se3_jobs(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_jobs_small(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se2_jobs_small(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se3_jobs_small(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_linked(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se2(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se3(const fksd::SimArgs* args);
@@ -115,6 +122,22 @@ sim_kernel_t path_small_kernel_for(int robot_type) {
         case FKS_ROBOT_SE2: return fks_simulate_se2_path_small;
         case FKS_ROBOT_SE3: return fks_simulate_se3_path_small;
         default: return fks_simulate_linked_path_small;
+    }
+}
+
+/* the job-batch instantiations (fks_forward_simulate_jobs): throughput and small-batch budget */
+sim_kernel_t jobs_kernel_for(int robot_type, bool lean) {
+    switch (robot_type) {
+        case FKS_ROBOT_SE2: return fks_simulate_se2_jobs;
+        case FKS_ROBOT_SE3: return fks_simulate_se3_jobs;
+        default: return lean ? fks_simulate_linked_lean_jobs : fks_simulate_linked_jobs;
+    }
+}
+sim_kernel_t jobs_small_kernel_for(int robot_type) {
+    switch (robot_type) {
+        case FKS_ROBOT_SE2: return fks_simulate_se2_jobs_small;
+        case FKS_ROBOT_SE3: return fks_simulate_se3_jobs_small;
+        default: return fks_simulate_linked_jobs_small;
     }
 }
 
@@ -295,9 +318,11 @@ struct fks_context {
     unsigned long long* h_counters = nullptr; /* pinned */
     fksd::SimArgs* d_args = nullptr;          /* kernel arguments, read through a pointer */
     fksd::SimArgs* h_args = nullptr;          /* pinned staging for d_args */
-    fksd::SimArgs* d_path_args = nullptr;     /* a path call's records, one per leg (SimArgs.path_legs) */
+    fksd::SimArgs* d_path_args = nullptr;     /* a path call's records, one per leg (SimArgs.path_legs), or a job
+                                                 batch's, one per job, then its job_first (SimArgs.job_first) */
     fksd::SimArgs* h_path_args = nullptr;     /* pinned staging for d_path_args */
     size_t cap_path_args = 0;
+    std::vector<unsigned char> jobs_stage;    /* fks_forward_simulate_jobs: the jobs' inputs, then outputs, end to end */
     bool pending = false;
     int pending_kind = 0; /* 0 = forward simulation, 1 = batched config check */
     hipStream_t pending_stream = nullptr;
@@ -1279,13 +1304,15 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
                                   uint64_t num_targets, uint64_t first_particle_id, int32_t allow_contacts,
                                   double* d_out_positions, uint8_t* d_out_collided, uint32_t* d_out_microsteps,
                                   uint32_t* d_out_resolver_iterations, uint32_t* d_out_error_flags, void* stream,
-                                  int32_t synchronize, const TraceDev* tr, double* d_pid_io = nullptr, uint64_t path_legs = 0) {
+                                  int32_t synchronize, const TraceDev* tr, double* d_pid_io = nullptr, uint64_t path_legs = 0,
+                                  const fks_job* jobs = nullptr, uint64_t num_jobs = 0) {
     /* path_legs > 0: fks_forward_simulate_path (d_targets holds the waypoints, the outputs are
-     * leg-major); 0: a plain call */
+     * leg-major); jobs: fks_forward_simulate_jobs (n is the jobs' sum, the particle arguments are
+     * each job's own, already checked by jobs_arguments); neither: a plain call */
     const bool path = path_legs > 0;
     if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
     if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
-    if (n > 0 && (!d_starts || !d_targets || !d_out_positions))
+    if (!jobs && n > 0 && (!d_starts || !d_targets || !d_out_positions))
         return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "null device buffer");
     if (n > 0 && num_targets != 1 && num_targets != n)
         return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "targets must be 1 or n (SPCS:792)");
@@ -1306,10 +1333,10 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     ctx->call_start = std::chrono::steady_clock::now();
     const uint64_t first_call = ctx->call_index;
     const uint64_t key = splitmix64(ctx->seed ^ splitmix64(first_call));
-    ctx->call_index += path ? path_legs : 1u;
+    ctx->call_index += path ? path_legs : (jobs ? num_jobs : 1u);
     std::memset(&ctx->last, 0, sizeof(ctx->last));
     ctx->last.particles = path ? n * path_legs : n; /* a path's counters are its chain's sums */
-    if (path && n == 0) return FKS_OK; /* the chain's calls would launch nothing either */
+    if ((path || jobs) && n == 0) return FKS_OK; /* the chain's calls would launch nothing either */
     fksd::SimArgs a;
     std::memset(&a, 0, sizeof(a));
     a.sdf_g = ctx->sdf_g;
@@ -1409,23 +1436,62 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     }
     /* a batch that fits the small-batch kernel's resident waves, whole particles, plain
      * simulation: that kernel (every particle has its wave from the start either way) */
-    const bool coop = !path && ctx->small_batch && ctx->cooperative && !tr && !ctx->individual_jacobians && !ctx->lean &&
+    const bool coop = !path && !jobs && ctx->small_batch && ctx->cooperative && !tr && !ctx->individual_jacobians && !ctx->lean &&
                       a.nseg == 1 && n > 0 && n <= (uint64_t)ctx->coop_particles;
     const bool small = !coop && ctx->small_batch && !tr && !ctx->individual_jacobians && !ctx->lean && a.nseg == 1 &&
                        n <= (uint64_t)ctx->small_grid_waves;
     const fksd::SimArgs* d_launch_args = ctx->d_args;
+    /* a job batch's records are followed by its job_first[num_jobs + 1], in whole records */
+    const size_t first_records = jobs ? ((size_t)(num_jobs + 1) * sizeof(uint32_t) + sizeof(fksd::SimArgs) - 1) / sizeof(fksd::SimArgs) : 0;
+    const size_t records = path ? (size_t)path_legs : (size_t)num_jobs + first_records;
     /* the previous call has settled, so the pinned staging copies are free */
-    if (path) {
+    if ((path || jobs) && records > ctx->cap_path_args) {
+        if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
+        ctx->h_path_args = nullptr;
+        ctx->cap_path_args = 0;
+        HIP_TRY(ctx, ensure(&ctx->d_path_args, records));
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_path_args, records * sizeof(fksd::SimArgs), 0));
+        ctx->cap_path_args = records;
+    }
+    if (jobs) {
+        /* one record per job: the same call over all n particles except for the job's key (the
+         * sequence's call index), its own arguments and outputs, and its slices of the segment
+         * arrays, which start at the job's first global particle */
+        uint32_t* h_first = reinterpret_cast<uint32_t*>(ctx->h_path_args + num_jobs);
+        a.job_first = reinterpret_cast<const uint32_t*>(ctx->d_path_args + num_jobs);
+        a.num_jobs = (uint32_t)num_jobs;
+        a.jobs_total = n;
+        uint64_t base = 0;
+        for (uint64_t j = 0; j < num_jobs; ++j) {
+            const fks_job& job = jobs[j];
+            fksd::SimArgs& r = ctx->h_path_args[j];
+            r = a;
+            const uint64_t job_key = splitmix64(ctx->seed ^ splitmix64(first_call + j));
+            r.key0 = (uint32_t)job_key;
+            r.key1 = (uint32_t)(job_key >> 32);
+            r.starts = job.starts;
+            r.targets = job.targets;
+            r.num_targets = job.num_targets;
+            r.n = job.n;
+            r.first_pid = job.first_particle_id;
+            r.allow_contacts = job.allow_contacts ? 1 : 0;
+            r.out_q = job.out_positions;
+            r.out_collided = job.out_collided;
+            r.out_micro = job.out_microsteps;
+            r.out_resolver = job.out_resolver_iterations;
+            r.out_err = job.out_error_flags;
+            r.seg_state = a.seg_state ? a.seg_state + base * a.seg_stride : nullptr;
+            r.seg_done = a.seg_done ? a.seg_done + base : nullptr;
+            r.job_base = (uint32_t)base;
+            h_first[j] = (uint32_t)base;
+            base += job.n;
+        }
+        h_first[num_jobs] = (uint32_t)base; /* == n */
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path_args, ctx->h_path_args, records * sizeof(fksd::SimArgs), hipMemcpyHostToDevice, s));
+        d_launch_args = ctx->d_path_args;
+    } else if (path) {
         /* one record per leg: the same call except for the leg's key (the chain's call index),
          * waypoints, start configurations (the leg before's output slice) and output slices */
-        if (path_legs > ctx->cap_path_args) {
-            if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
-            ctx->h_path_args = nullptr;
-            ctx->cap_path_args = 0;
-            HIP_TRY(ctx, ensure(&ctx->d_path_args, (size_t)path_legs));
-            HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_path_args, (size_t)path_legs * sizeof(fksd::SimArgs), 0));
-            ctx->cap_path_args = (size_t)path_legs;
-        }
         const uint64_t W = (uint64_t)ctx->R.W;
         a.path_legs = (uint32_t)path_legs;
         /* whole legs and a wave for every particle: the wave keeps its particle through all legs */
@@ -1458,19 +1524,20 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     /* the plain throughput path runs the robot's shape-specialised kernel: built (or fetched
      * from a cache) here at the first such launch; a failure keeps the generic kernel and is
      * reported by fks_get_specialization / fks_get_last_error, not by this call */
-    if (ctx->spec_pending && !path && !tr && !small && !coop && !ctx->individual_jacobians) {
+    if (ctx->spec_pending && !path && !jobs && !tr && !small && !coop && !ctx->individual_jacobians) {
         ctx->spec_pending = false;
         const std::string keep = ctx->last_error;
         if (spec_prepare(ctx) != FKS_OK) ctx->last_error = keep + (keep.empty() ? "" : "; ") + ctx->last_error;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
     }
     /* (a path runs the generic path kernels: it neither builds nor launches the shape's module) */
-    const bool shaped = ctx->spec_fn && !path && !tr && !small && !coop && !ctx->individual_jacobians;
+    const bool shaped = ctx->spec_fn && !path && !jobs && !tr && !small && !coop && !ctx->individual_jacobians;
     /* a small batch runs the shape's small-batch kernel once the robot's module is built (it is
      * never built for a small batch: robots only ever simulated in small batches cost no compile) */
-    const bool shaped_small = !path && small && ctx->spec_fn && ctx->spec_small_fn;
+    const bool shaped_small = !path && !jobs && small && ctx->spec_fn && ctx->spec_small_fn;
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    ctx->last_kernel = path ? (small ? FKS_KERNEL_PATH_SMALL_BATCH : FKS_KERNEL_PATH)
+    ctx->last_kernel = jobs ? (small ? FKS_KERNEL_JOBS_SMALL_BATCH : FKS_KERNEL_JOBS)
+                       : path ? (small ? FKS_KERNEL_PATH_SMALL_BATCH : FKS_KERNEL_PATH)
                        : tr ? FKS_KERNEL_TRACED
                           : (shaped ? FKS_KERNEL_SHAPED
                                     : shaped_small ? FKS_KERNEL_SHAPED_SMALL_BATCH
@@ -1492,6 +1559,9 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     } else if (coop) {
         hipLaunchKernelGGL(coop_kernel_for(ctx->R.type), dim3((uint32_t)n), dim3(64 * ctx->coop_waves), ctx->coop_lds_bytes, s,
                            static_cast<const fksd::SimArgs*>(ctx->d_args));
+    } else if (jobs) {
+        hipLaunchKernelGGL(small ? jobs_small_kernel_for(ctx->R.type) : jobs_kernel_for(ctx->R.type, ctx->lean), dim3(grid),
+                           dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
     } else if (path) {
         hipLaunchKernelGGL(small ? path_small_kernel_for(ctx->R.type) : path_kernel_for(ctx->R.type, ctx->lean), dim3(grid),
                            dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
@@ -1784,6 +1854,121 @@ fks_status fks_forward_simulate_path(fks_context* ctx, const double* starts, uin
     if (out_resolver_iterations)
         HIP_TRY(ctx, hipMemcpy(out_resolver_iterations, ctx->d_res, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (out_error_flags) HIP_TRY(ctx, hipMemcpy(out_error_flags, ctx->d_err, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
+    return FKS_OK;
+}
+
+/* what both jobs entries refuse before anything is staged or counted; *total: the sum of n */
+static fks_status jobs_arguments(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs, uint64_t* total) {
+    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
+    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
+    if (num_jobs == 0 || !jobs) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "a job batch needs at least one job");
+    if (num_jobs > FKS_MAX_JOBS) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 65536 jobs per batch");
+    if (ctx->individual_jacobians)
+        return fail(ctx, FKS_ERR_UNSUPPORTED, "no jobs kernel with individual Jacobians (fks_set_individual_jacobians): issue plain calls");
+    uint64_t sum = 0;
+    for (uint64_t j = 0; j < num_jobs; ++j) {
+        const fks_job& job = jobs[j];
+        if (job.num_targets != 1 && job.num_targets != job.n)
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": targets must be 1 or n (SPCS:792)");
+        if (job.n > 0 && (!job.starts || !job.targets || !job.out_positions))
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": null starts, targets or out_positions");
+        if (job.n > 0xffffffffull || sum + job.n > 0xffffffffull)
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per batch");
+        sum += job.n;
+    }
+    *total = sum;
+    return FKS_OK;
+}
+
+fks_status fks_forward_simulate_jobs_device(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs, void* stream,
+                                            int32_t synchronize) {
+    uint64_t total = 0;
+    const fks_status st = jobs_arguments(ctx, jobs, num_jobs, &total);
+    if (st != FKS_OK) return st;
+    return simulate_device(ctx, nullptr, total, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, stream, synchronize,
+                           nullptr, nullptr, 0, jobs, num_jobs);
+}
+
+fks_status fks_forward_simulate_jobs(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs) {
+    uint64_t N = 0;
+    fks_status st = jobs_arguments(ctx, jobs, num_jobs, &N);
+    if (st != FKS_OK) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = settle(ctx);
+    if (st != FKS_OK) return st;
+    if (N == 0) return simulate_device(ctx, nullptr, 0, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1,
+                                       nullptr, nullptr, 0, jobs, num_jobs);
+    /* the staging buffers of the plain host calls: d_starts holds every job's starts and then
+     * every job's targets, so the inputs go up in one copy */
+    const size_t W = (size_t)ctx->R.W;
+    uint64_t NT = 0;
+    for (uint64_t j = 0; j < num_jobs; ++j) NT += jobs[j].n > 0 ? jobs[j].num_targets : 0;
+    const uint64_t rows = N + NT;
+    if (rows > ctx->cap_particles) {
+        HIP_TRY(ctx, ensure(&ctx->d_starts, rows * W));
+        HIP_TRY(ctx, ensure(&ctx->d_out, rows * W));
+        HIP_TRY(ctx, ensure(&ctx->d_coll, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_micro, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_res, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_err, rows));
+        ctx->cap_particles = rows;
+    }
+    const size_t in_bytes = rows * W * sizeof(double);
+    const size_t q_bytes = N * W * sizeof(double), u_bytes = N * sizeof(uint32_t);
+    ctx->jobs_stage.resize(std::max(in_bytes, q_bytes + 3 * u_bytes + N));
+    double* h_in = reinterpret_cast<double*>(ctx->jobs_stage.data());
+    std::vector<fks_job> dev(jobs, jobs + num_jobs); /* the same jobs over the staging buffers */
+    uint64_t at = 0, tat = N;
+    for (uint64_t j = 0; j < num_jobs; ++j) {
+        fks_job& d = dev[j];
+        if (d.n == 0) continue;
+        std::memcpy(h_in + at * W, d.starts, d.n * W * sizeof(double));
+        std::memcpy(h_in + tat * W, d.targets, d.num_targets * W * sizeof(double));
+        d.starts = ctx->d_starts + at * W;
+        d.targets = ctx->d_starts + tat * W;
+        d.out_positions = ctx->d_out + at * W;
+        d.out_collided = ctx->d_coll + at;
+        d.out_microsteps = ctx->d_micro + at;
+        d.out_resolver_iterations = ctx->d_res + at;
+        d.out_error_flags = ctx->d_err + at;
+        at += d.n;
+        tat += d.num_targets;
+    }
+    HIP_TRY(ctx, hipMemcpy(ctx->d_starts, h_in, in_bytes, hipMemcpyHostToDevice));
+    st = simulate_device(ctx, nullptr, N, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, 0,
+                         dev.data(), num_jobs);
+    if (st != FKS_OK) return st;
+    /* one copy down per output array, then each job's rows to its own arrays */
+    double* h_q = reinterpret_cast<double*>(ctx->jobs_stage.data());
+    uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + N * W);
+    uint32_t* h_res = h_micro + N;
+    uint32_t* h_err = h_res + N;
+    uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + N);
+    bool want_coll = false, want_micro = false, want_res = false, want_err = false;
+    for (uint64_t j = 0; j < num_jobs; ++j) {
+        if (jobs[j].n == 0) continue;
+        want_coll |= jobs[j].out_collided != nullptr;
+        want_micro |= jobs[j].out_microsteps != nullptr;
+        want_res |= jobs[j].out_resolver_iterations != nullptr;
+        want_err |= jobs[j].out_error_flags != nullptr;
+    }
+    HIP_TRY(ctx, hipMemcpy(h_q, ctx->d_out, q_bytes, hipMemcpyDeviceToHost));
+    if (want_coll) HIP_TRY(ctx, hipMemcpy(h_coll, ctx->d_coll, N, hipMemcpyDeviceToHost));
+    if (want_micro) HIP_TRY(ctx, hipMemcpy(h_micro, ctx->d_micro, u_bytes, hipMemcpyDeviceToHost));
+    if (want_res) HIP_TRY(ctx, hipMemcpy(h_res, ctx->d_res, u_bytes, hipMemcpyDeviceToHost));
+    if (want_err) HIP_TRY(ctx, hipMemcpy(h_err, ctx->d_err, u_bytes, hipMemcpyDeviceToHost));
+    at = 0;
+    for (uint64_t j = 0; j < num_jobs; ++j) {
+        const fks_job& job = jobs[j];
+        if (job.n == 0) continue;
+        std::memcpy(job.out_positions, h_q + at * W, job.n * W * sizeof(double));
+        if (job.out_collided) std::memcpy(job.out_collided, h_coll + at, job.n);
+        if (job.out_microsteps) std::memcpy(job.out_microsteps, h_micro + at, job.n * sizeof(uint32_t));
+        if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations, h_res + at, job.n * sizeof(uint32_t));
+        if (job.out_error_flags) std::memcpy(job.out_error_flags, h_err + at, job.n * sizeof(uint32_t));
+        at += job.n;
+    }
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
     return FKS_OK;
 }

@@ -396,6 +396,17 @@ struct SimArgs {
      * resident waves, so a wave keeps its particle across every boundary */
     uint32_t path_legs;
     uint32_t path_carry;
+    /* job batches (fks_forward_simulate_jobs, the *_jobs kernels): the kernel's argument is an
+     * array of num_jobs records, one per job, equal except for what a job owns: its RNG key, its
+     * starts, targets, num_targets, n, first_pid and allow_contacts, its output pointers, and its
+     * slices of seg_state / seg_done (the batch's arrays offset by job_base particles).  The
+     * ticket space is one plain call's over jobs_total = sum of n particles; job_first
+     * [num_jobs + 1] holds the jobs' first global particles (job_first[num_jobs] ==
+     * jobs_total; empty jobs make equal neighbours) and job_base is the record's own entry */
+    const uint32_t* job_first;
+    uint32_t num_jobs;
+    uint32_t job_base;
+    uint64_t jobs_total;
 };
 
 enum {

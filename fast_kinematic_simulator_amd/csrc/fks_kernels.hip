@@ -3895,13 +3895,46 @@ __device__ __forceinline__ void kinematics(const SimArgs* __restrict__ args, dou
     }
 }
 
+/* The job of global particle g in a job batch (SimArgs.job_first): the last j with
+ * job_first[j] <= g, an upper bound because empty jobs make equal neighbours.  A 64-ary
+ * search over the num_jobs + 1 prefix entries: each step the wave's lanes compare 64 evenly
+ * spaced entries (one vector load and a ballot), so 63 jobs cost one step, 4,095 two and the
+ * 65,536 cap three.  Every lane takes part; the result is wave-uniform (an SGPR) */
+__device__ __forceinline__ uint32_t job_of(const SimArgs* __restrict__ args, uint32_t g, int ln) {
+    const uint32_t* __restrict__ first = args->job_first;
+    uint32_t lo = 0, count = args->num_jobs + 1u; /* first[lo] <= g throughout (first[0] == 0) */
+    while (count > (uint32_t)kWave) {
+        const uint32_t stride = (count + (uint32_t)kWave - 1u) / (uint32_t)kWave;
+        const uint32_t at = (uint32_t)ln * stride;
+        const bool le = at < count && first[lo + at] <= g;
+        const uint32_t c = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(le)); /* >= 1: lane 0 reads first[lo] */
+        const uint32_t rest = count - (c - 1u) * stride;
+        lo += (c - 1u) * stride;
+        count = rest < stride ? rest : stride;
+    }
+    const bool le = (uint32_t)ln < count && first[lo + (uint32_t)ln] <= g;
+    const uint32_t c = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(le));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(lo + c - 1u));
+}
+
 /* PATH: the waypoint-path kernels (fks_forward_simulate_path).  args is then an array of
  * A.path_legs records, one per leg (SimArgs.path_legs), and a particle's ticket space is
  * path_legs x nseg segments: a leg boundary is one more segment boundary, at which the
- * particle is reset as the next call of a chain of plain calls would reset it */
-template <int RT, bool TR, bool IND = false, bool LEAN = false, int COOP = 0, bool PATH = false>
+ * particle is reset as the next call of a chain of plain calls would reset it.
+ * JOBS: the job-batch kernels (fks_forward_simulate_jobs).  args is an array of A.num_jobs
+ * records, one per job (SimArgs.job_first), and the ticket space is that of one plain call
+ * over the jobs' particles laid end to end: ticket t is segment t / jobs_total of global
+ * particle t % jobs_total, which job_of() maps to its job's record */
+template <int RT, bool TR, bool IND = false, bool LEAN = false, int COOP = 0, bool PATH = false, bool JOBS = false>
 __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ args, double* lds_mem) {
     const SimArgs& A = *args;
+    /* particles in the ticket space: the call's, or all jobs' (equal in every record) */
+    auto batch_n = [&]() -> uint64_t {
+        if constexpr (JOBS)
+            return args->jobs_total;
+        else
+            return A.n;
+    };
     const RobotDev& R = A.R;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); /* wave-uniform: LDS bases stay in SGPRs */
     double* shared = lds_mem;
@@ -3991,10 +4024,10 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
         } else {
             if (ln == 0) {
                 const uint64_t t = __hip_atomic_fetch_add(A.queue, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint64_t sg = (A.n > 0) ? t / A.n : (uint64_t)nsegs;
+                const uint64_t sg = (batch_n() > 0) ? t / batch_n() : (uint64_t)nsegs;
                 uint32_t run = 1;
                 if (sg > 0 && sg < (uint64_t)nsegs) {
-                    uint32_t* done = A.seg_done + (t - sg * A.n);
+                    uint32_t* done = A.seg_done + (t - sg * batch_n());
                     uint32_t v = __hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     run = (v == (uint32_t)sg &&
                            __hip_atomic_compare_exchange_strong(done, &v, (uint32_t)sg | kSegClaimed, __ATOMIC_RELAXED,
@@ -4009,7 +4042,7 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             ticket = *next_particle;
             const uint32_t run = *seg_seen;
             wsync();
-            if ((A.n > 0 ? ticket / A.n : (uint64_t)nsegs) >= (uint64_t)nsegs) {
+            if ((batch_n() > 0 ? ticket / batch_n() : (uint64_t)nsegs) >= (uint64_t)nsegs) {
                 /* the queue is drained: this wave slot idles from here to the kernel's end */
                 const uint64_t bytes = wave_sum_u64(s.lane_bytes);
                 if (ln == 0) {
@@ -4048,8 +4081,8 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             else
                 __builtin_amdgcn_s_setprio(0);
         }
-        uint64_t seg = ticket / A.n;
-        const uint64_t local = ticket - seg * A.n;
+        uint64_t seg = ticket / batch_n();
+        const uint64_t global = ticket - seg * batch_n(); /* the particle in the ticket space */
         uint32_t leg = 0;
         if constexpr (PATH) {
             /* segment seg of the path is segment seg % nseg of leg seg / nseg (wave-uniform, so
@@ -4059,8 +4092,11 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
         }
         /* from here to the end of the segment A is the leg's record: its key, targets, start
          * configurations and output slices (the plain kernels have one record) */
-        const SimArgs& A = PATH ? args[leg] : *args;
-        if constexpr (PATH) s.A = &A;
+        if constexpr (JOBS) leg = job_of(args, (uint32_t)global, ln);
+        const SimArgs& A = (PATH || JOBS) ? args[leg] : *args;
+        if constexpr (PATH || JOBS) s.A = &A;
+        /* the particle within its call: a job's records index their own arrays */
+        const uint64_t local = JOBS ? global - A.job_base : global;
         const uint32_t step_begin = (uint32_t)seg * A.seg_steps;
         const uint32_t step_end = (seg + 1 == (uint64_t)nseg) ? A.T : step_begin + A.seg_steps;
         double* st = A.seg_state + local * (uint64_t)A.seg_stride; /* nseg > 1 only */
@@ -4280,7 +4316,7 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
                     if (more && A.path_carry) heavy = true;
                 }
                 if (more) {
-                    const uint64_t next_ticket = next_seg * A.n + local;
+                    const uint64_t next_ticket = next_seg * batch_n() + global;
                     const uint64_t issued =
                         heavy ? ~0ull : __hip_atomic_load(A.queue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (issued > next_ticket &&
@@ -4293,7 +4329,7 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             wsync();
             const uint32_t cont = *seg_seen;
             if (cont) {
-                carry = next_seg * A.n + local;
+                carry = next_seg * batch_n() + global;
                 carry_heavy = cont == 2u;
             }
         }
@@ -4455,6 +4491,37 @@ extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_path_small(co
 extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_path_small(const SimArgs* __restrict__ args) {
     extern __shared__ __attribute__((aligned(16))) double lds_mem[];
     simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true>(args, lds_mem);
+}
+
+/* job batches (fks_forward_simulate_jobs): JOBS instantiations at the throughput budget ... */
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_jobs(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, false, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_jobs(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, true, 0, false, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_jobs(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, false, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_jobs(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, false, true>(args, lds_mem);
+}
+/* ... and at the small-batch budget, for batches whose jobs together fit its resident waves */
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_linked_jobs_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, false, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_jobs_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, false, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_jobs_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, false, true>(args, lds_mem);
 }
 
 extern "C" __global__ void FKS_KERNEL_ATTRS fks_check_configs_linked(const SimArgs* __restrict__ args) {

@@ -211,6 +211,8 @@ fks_status fks_multi_set_robot(fks_multi_context* m, const fks_robot_desc* robot
     return FKS_OK;
 }
 
+static void sum_counters(fks_multi_context* m, int32_t ndev, std::chrono::steady_clock::time_point t0);
+
 /* fks_multi_forward_simulate (legs == 0) and fks_multi_forward_simulate_path (legs >= 1: targets
  * holds the waypoints [legs][num_targets][W], the outputs are leg-major [legs][n]...) */
 static fks_status multi_simulate(fks_multi_context* m, const double* starts, uint64_t n, const double* targets, uint64_t legs,
@@ -301,6 +303,12 @@ static fks_status multi_simulate(fks_multi_context* m, const double* starts, uin
     });
     const fks_status st = collect_status(m, ndev);
     if (st != FKS_OK) return st;
+    sum_counters(m, ndev, t0);
+    return FKS_OK;
+}
+
+/* the call's counters: the devices' sums, the longest device's kernel time */
+static void sum_counters(fks_multi_context* m, int32_t ndev, std::chrono::steady_clock::time_point t0) {
     std::memset(&m->last, 0, sizeof(m->last));
     for (int32_t g = 0; g < ndev; ++g) {
         const fks_call_counters& c = m->devices[(size_t)g].counters;
@@ -317,7 +325,6 @@ static fks_status multi_simulate(fks_multi_context* m, const double* starts, uin
     }
     m->last.calls = 1;
     m->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return FKS_OK;
 }
 
 fks_status fks_multi_forward_simulate(fks_multi_context* m, const double* starts, uint64_t n, const double* targets,
@@ -335,6 +342,134 @@ fks_status fks_multi_forward_simulate_path(fks_multi_context* m, const double* s
     if (num_legs == 0) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "a path needs at least one leg");
     return multi_simulate(m, starts, n, waypoints, num_legs, num_targets, allow_contacts, out_positions, out_collided,
                           out_microsteps, out_resolver_iterations, out_error_flags);
+}
+
+fks_status fks_multi_forward_simulate_jobs(fks_multi_context* m, const fks_job* jobs, uint64_t num_jobs) {
+    if (!m) return FKS_ERR_INVALID_ARGUMENT;
+    if (m->width <= 0) return mfail(m, FKS_ERR_NO_ROBOT, "fks_multi_set_robot has not been called");
+    if (num_jobs == 0 || !jobs) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "a job batch needs at least one job");
+    if (num_jobs > FKS_MAX_JOBS) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "at most 65536 jobs per batch");
+    std::vector<uint64_t> first((size_t)num_jobs + 1, 0); /* the jobs' first particles in the concatenated range */
+    for (uint64_t j = 0; j < num_jobs; ++j) {
+        const fks_job& job = jobs[j];
+        if (job.num_targets != 1 && job.num_targets != job.n)
+            return mfail(m, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": targets must be 1 or n (SPCS:792)");
+        if (job.n > 0 && (!job.starts || !job.targets || !job.out_positions))
+            return mfail(m, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": null starts, targets or out_positions");
+        if (job.n > 0xffffffffull || first[j] + job.n > 0xffffffffull)
+            return mfail(m, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per batch");
+        first[j + 1] = first[j] + job.n;
+    }
+    const uint64_t N = first[num_jobs];
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t W = (size_t)m->width;
+    const int32_t ndev = active_count(m);
+    const uint64_t call = m->call_index;
+    /* one host thread per device: stage in, launch, stage out (the devices run concurrently) */
+    on_device_threads(ndev, [&](int32_t g) {
+        auto& d = m->devices[(size_t)g];
+        d.status = FKS_OK;
+        d.error.clear();
+        std::memset(&d.counters, 0, sizeof(d.counters));
+        uint64_t lo = 0, hi = 0;
+        fks_shard_bounds(N, ndev, g, &lo, &hi);
+        const uint64_t k = hi - lo;
+        /* the device's jobs: of every job the shard meets its rows [a, b), every other job empty */
+        std::vector<fks_job> dev((size_t)num_jobs);
+        std::vector<uint64_t> row0((size_t)num_jobs, 0); /* the sub-range's first row within its job */
+        uint64_t nt = 0;
+        for (uint64_t j = 0; j < num_jobs; ++j) {
+            const uint64_t a = std::max(first[j], lo), b = std::min(first[j + 1], hi);
+            fks_job& s = dev[j];
+            std::memset(&s, 0, sizeof(s));
+            s.num_targets = 1; /* an empty job: 1 is always accepted */
+            if (a >= b) continue;
+            row0[j] = a - first[j];
+            s.n = b - a;
+            s.num_targets = (jobs[j].num_targets == jobs[j].n && jobs[j].n != 1) ? s.n : 1;
+            s.first_particle_id = jobs[j].first_particle_id + row0[j];
+            s.allow_contacts = jobs[j].allow_contacts;
+            nt += s.num_targets;
+        }
+        DCTX(d, fks_set_call_index(d.ctx, call), "fks_set_call_index");
+        DHIP(d, hipSetDevice(d.device));
+        if (k > d.cap) {
+            DHIP(d, grow(&d.d_starts, k * W));
+            DHIP(d, grow(&d.d_out, k * W));
+            DHIP(d, grow(&d.d_coll, k));
+            DHIP(d, grow(&d.d_micro, k));
+            DHIP(d, grow(&d.d_res, k));
+            DHIP(d, grow(&d.d_err, k));
+            d.cap = k;
+        }
+        if (nt > d.cap_targets) {
+            DHIP(d, grow(&d.d_targets, nt * W));
+            d.cap_targets = nt;
+        }
+        const size_t in_bytes = (k + nt) * W * sizeof(double);
+        const size_t out_bytes = k * W * sizeof(double) + k * (1 + 3 * sizeof(uint32_t));
+        DHIP(d, grow_pinned(&d.h_in, &d.cap_h_in, in_bytes));
+        DHIP(d, grow_pinned(&d.h_out, &d.cap_h_out, out_bytes));
+        double* h_starts = reinterpret_cast<double*>(d.h_in);
+        double* h_targets = h_starts + k * W;
+        uint64_t at = 0, tat = 0;
+        for (uint64_t j = 0; j < num_jobs; ++j) {
+            fks_job& s = dev[j];
+            if (s.n == 0) continue;
+            std::memcpy(h_starts + at * W, jobs[j].starts + row0[j] * W, s.n * W * sizeof(double));
+            std::memcpy(h_targets + tat * W, jobs[j].targets + (s.num_targets == 1 && jobs[j].num_targets == 1 ? 0 : row0[j]) * W,
+                        s.num_targets * W * sizeof(double));
+            s.starts = d.d_starts + at * W;
+            s.targets = d.d_targets + tat * W;
+            s.out_positions = d.d_out + at * W;
+            s.out_collided = d.d_coll + at;
+            s.out_microsteps = d.d_micro + at;
+            s.out_resolver_iterations = d.d_res + at;
+            s.out_error_flags = d.d_err + at;
+            at += s.n;
+            tat += s.num_targets;
+        }
+        if (k > 0) {
+            DHIP(d, hipMemcpyAsync(d.d_starts, h_starts, k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
+            DHIP(d, hipMemcpyAsync(d.d_targets, h_targets, nt * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
+        }
+        DCTX(d, fks_forward_simulate_jobs_device(d.ctx, dev.data(), num_jobs, d.stream, 0), "fks_forward_simulate_jobs_device");
+        if (k == 0) {
+            DCTX(d, fks_get_last_call_counters(d.ctx, &d.counters), "fks_get_last_call_counters"); /* settles */
+            std::memset(&d.counters, 0, sizeof(d.counters));
+            return;
+        }
+        double* h_q = reinterpret_cast<double*>(d.h_out);
+        uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + k * W);
+        uint32_t* h_res = h_micro + k;
+        uint32_t* h_err = h_res + k;
+        uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + k);
+        DHIP(d, hipMemcpyAsync(h_q, d.d_out, k * W * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_micro, d.d_micro, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_res, d.d_res, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_err, d.d_err, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_coll, d.d_coll, k, hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipStreamSynchronize(d.stream));
+        at = 0;
+        for (uint64_t j = 0; j < num_jobs; ++j) {
+            const fks_job& s = dev[j];
+            const fks_job& job = jobs[j];
+            if (s.n == 0) continue;
+            const uint64_t dst = row0[j];
+            std::memcpy(job.out_positions + dst * W, h_q + at * W, s.n * W * sizeof(double));
+            if (job.out_collided) std::memcpy(job.out_collided + dst, h_coll + at, s.n);
+            if (job.out_microsteps) std::memcpy(job.out_microsteps + dst, h_micro + at, s.n * sizeof(uint32_t));
+            if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations + dst, h_res + at, s.n * sizeof(uint32_t));
+            if (job.out_error_flags) std::memcpy(job.out_error_flags + dst, h_err + at, s.n * sizeof(uint32_t));
+            at += s.n;
+        }
+        DCTX(d, fks_get_last_call_counters(d.ctx, &d.counters), "fks_get_last_call_counters"); /* settles the launch */
+    });
+    const fks_status st = collect_status(m, ndev);
+    if (st != FKS_OK) return st; /* a refusal by the devices' contexts leaves the call index where it was */
+    m->call_index = call + num_jobs;
+    sum_counters(m, ndev, t0);
+    return FKS_OK;
 }
 
 fks_status fks_multi_set_active_devices(fks_multi_context* m, int32_t count) {

@@ -272,6 +272,17 @@ class HipParticleContactSimulator:
         return {"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
                 "error_flags": errors}
 
+    def forward_simulate_jobs_arrays(self, robot: RobotDescription, jobs) -> list:
+        """Many independent calls in one launch (fks_forward_simulate_jobs).  jobs: a sequence of
+        (starts (n, W), targets (1 or n, W), allow_contacts).  Returns a list of the dicts
+        forward_simulate_arrays returns: job j is what forward_simulate_arrays returns at call
+        index get_call_index() + j, byte for byte; the call index advances by len(jobs)."""
+        self.set_robot(robot)
+        array, results, _keep = _host_jobs(jobs, robot.config_width)
+        st = self._lib.fks_forward_simulate_jobs(self._ctx, array, len(results))
+        _capi.check(st, self._ctx, "fks_forward_simulate_jobs")
+        return [_job_result(r) for r in results]
+
     def forward_simulate_mutable_arrays(self, robot: RobotDescription, start_positions, target_positions, allow_contacts: bool,
                                         controller_state) -> dict:
         """ForwardSimulateMutableRobot (SPCS:843-919) for a batch (fks_forward_simulate_mutable):
@@ -529,6 +540,48 @@ class HipParticleContactSimulator:
             ctypes.c_void_p(d_out_microsteps or None), ctypes.c_void_p(d_out_resolver_iterations or None),
             ctypes.c_void_p(d_out_error_flags or None), ctypes.c_void_p(stream or None), 1 if synchronize else 0)
         _capi.check(st, self._ctx, "fks_forward_simulate_path_device")
+    def forward_simulate_jobs_device(self, robot: RobotDescription, jobs, stream=0, synchronize=False):
+        """fks_forward_simulate_jobs_device: jobs is a sequence of dicts with the fields of fks_job
+        (d_starts, n, d_targets, num_targets, allow_contacts, d_out_positions and optionally
+        first_particle_id, d_out_collided, d_out_microsteps, d_out_resolver_iterations,
+        d_out_error_flags), every buffer a device pointer (int) as in forward_simulate_device."""
+        self.set_robot(robot)
+        array = (_capi.Job * max(len(jobs), 1))()
+        for j, job in enumerate(jobs):
+            array[j] = _capi.Job(
+                job["d_starts"] or None, int(job["n"]), job["d_targets"] or None, int(job["num_targets"]),
+                int(job.get("first_particle_id", 0)), 1 if job["allow_contacts"] else 0, 0, job["d_out_positions"] or None,
+                job.get("d_out_collided") or None, job.get("d_out_microsteps") or None,
+                job.get("d_out_resolver_iterations") or None, job.get("d_out_error_flags") or None)
+        st = self._lib.fks_forward_simulate_jobs_device(self._ctx, array, len(jobs), ctypes.c_void_p(stream or None),
+                                                        1 if synchronize else 0)
+        _capi.check(st, self._ctx, "fks_forward_simulate_jobs_device")
+
+
+def _host_jobs(jobs, W: int):
+    """The fks_job array of (starts, targets, allow_contacts) jobs over host arrays: the ctypes
+    array, per job its (targets' count, output arrays), and the input arrays to keep alive."""
+    array = (_capi.Job * max(len(jobs), 1))()
+    results, keep = [], []
+    for j, (start_positions, target_positions, allow_contacts) in enumerate(jobs):
+        starts = np.ascontiguousarray(np.asarray(start_positions, dtype=np.float64).reshape(-1, W))
+        targets = np.ascontiguousarray(np.asarray(target_positions, dtype=np.float64).reshape(-1, W))
+        n = starts.shape[0]
+        out = {"positions": np.zeros((n, W), dtype=np.float64), "collided": np.zeros(n, dtype=np.uint8),
+               "microsteps": np.zeros(n, dtype=np.uint32), "resolver_iterations": np.zeros(n, dtype=np.uint32),
+               "error_flags": np.zeros(n, dtype=np.uint32)}
+        ptr = (lambda a: a.ctypes.data) if n > 0 else (lambda a: None)
+        array[j] = _capi.Job(ptr(starts), n, targets.ctypes.data if targets.size else None, targets.shape[0], 0,
+                             1 if allow_contacts else 0, 0, ptr(out["positions"]), ptr(out["collided"]), ptr(out["microsteps"]),
+                             ptr(out["resolver_iterations"]), ptr(out["error_flags"]))
+        results.append(out)
+        keep.append((starts, targets))
+    return array, results, keep
+
+
+def _job_result(out: dict) -> dict:
+    return {"positions": out["positions"], "collided": out["collided"].astype(bool), "microsteps": out["microsteps"],
+            "resolver_iterations": out["resolver_iterations"], "error_flags": out["error_flags"]}
 
 
 def _path_waypoints(waypoints, W: int, n: int):
@@ -649,6 +702,16 @@ class MultiDeviceSimulator:
         self._check(st, "fks_multi_forward_simulate_path")
         return {"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
                 "error_flags": errors}
+
+    def forward_simulate_jobs_arrays(self, robot: RobotDescription, jobs) -> list:
+        """fks_multi_forward_simulate_jobs: HipParticleContactSimulator.forward_simulate_jobs_arrays
+        with the jobs' particles, laid end to end, sharded over the devices (bit-identical to one
+        device)."""
+        self.set_robot(robot)
+        array, results, _keep = _host_jobs(jobs, robot.config_width)
+        st = self._lib.fks_multi_forward_simulate_jobs(self._ctx, array, len(results))
+        self._check(st, "fks_multi_forward_simulate_jobs")
+        return [_job_result(r) for r in results]
 
     def check_config_collisions(self, robot: RobotDescription, configs, inflation_ratio: float):
         """Batched CheckConfigCollision (SPCS:1398-1416) sharded over the devices:

@@ -288,6 +288,78 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
         }
         return out;
     }
+    /* Not part of SimulatorInterface: many independent calls in one launch
+     * (fks_forward_simulate_jobs), for the planner's stream of small ForwardSimulateRobots /
+     * ReverseSimulateRobots calls (their semantics are the same, SPCS:838-841).  A job is one
+     * such call's arguments; results[j] is what the j-th of jobs.size() plain calls issued one
+     * after the other returns, bit for bit.  The device count is chosen per batch from the jobs'
+     * particles together. */
+    struct SimulationJob {
+        std::vector<Configuration, ConfigAlloc> start_positions;
+        std::vector<Configuration, ConfigAlloc> target_positions; /* 1 or start_positions.size() */
+        bool allow_contacts = false;
+    };
+    std::vector<std::vector<SimulationResult>> ForwardSimulateRobotsJobs(const std::shared_ptr<BaseRobotType>& immutable_robot,
+                                                                         const std::vector<SimulationJob>& jobs) {
+        if (jobs.empty()) throw std::invalid_argument("a job batch needs at least one job");
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        SetRobot(robot);
+        const size_t J = jobs.size();
+        std::vector<double> s, t;
+        std::vector<size_t> ns(J), nts(J);
+        size_t N = 0;
+        for (size_t j = 0; j < J; ++j) {
+            const SimulationJob& job = jobs[j];
+            const size_t n = job.start_positions.size(), nt = n > 0 ? job.target_positions.size() : 0;
+            if (n > 0 && nt != 1 && nt != n) throw std::invalid_argument("a job must hold 1 or start_positions.size() targets (SPCS:792)");
+            ns[j] = n;
+            nts[j] = nt;
+            N += n;
+            for (const auto& c : job.start_positions) {
+                const std::vector<double> f = robot.ToFlat(c);
+                s.insert(s.end(), f.begin(), f.end());
+            }
+            for (size_t i = 0; i < nt; ++i) {
+                const std::vector<double> f = robot.ToFlat(job.target_positions[i]);
+                t.insert(t.end(), f.begin(), f.end());
+            }
+        }
+        const size_t W = N ? s.size() / N : 0;
+        std::vector<double> q(N * W);
+        std::vector<uint8_t> collided(N);
+        last_micro_.assign(N, 0);
+        last_resolver_.assign(N, 0);
+        last_errors_.assign(N, 0);
+        std::vector<fks_job> cj(J);
+        size_t at = 0, tat = 0;
+        for (size_t j = 0; j < J; ++j) {
+            fks_job& c = cj[j];
+            c = fks_job();
+            c.starts = s.data() + at * W;
+            c.n = ns[j];
+            c.targets = t.data() + tat * W;
+            c.num_targets = ns[j] > 0 ? nts[j] : 1;
+            c.allow_contacts = jobs[j].allow_contacts ? 1 : 0;
+            c.out_positions = q.data() + at * W;
+            c.out_collided = collided.data() + at;
+            c.out_microsteps = last_micro_.data() + at;
+            c.out_resolver_iterations = last_resolver_.data() + at;
+            c.out_error_flags = last_errors_.data() + at;
+            at += ns[j];
+            tat += nts[j];
+        }
+        dev_->simulate_jobs(cj.data(), J, "ForwardSimulateRobotsJobs");
+        std::vector<std::vector<SimulationResult>> out(J);
+        size_t row = 0;
+        for (size_t j = 0; j < J; ++j) {
+            out[j].reserve(ns[j]);
+            for (size_t i = 0; i < ns[j]; ++i, ++row)
+                out[j].emplace_back(robot.FromFlat(q.data() + row * W),
+                                    nts[j] == ns[j] ? jobs[j].target_positions[i] : jobs[j].target_positions[0],
+                                    collided[row] != 0, true);
+        }
+        return out;
+    }
     /* SPCS:824-829: a clone reset to the start (controllers zeroed) */
     SimulationResult ForwardSimulateRobot(const std::shared_ptr<BaseRobotType>& immutable_robot, const Configuration& start_position,
                                           const Configuration& target_position, const bool allow_contacts,

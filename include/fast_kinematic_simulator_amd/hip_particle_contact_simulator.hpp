@@ -58,6 +58,14 @@ struct SimulationResult {
     uint32_t error_flags = 0; /* FKS_PARTICLE_ERR_* */
 };
 
+/* One of the independent calls of ForwardSimulateRobotsJobs: the arguments of one
+ * ForwardSimulateRobots call (target_positions holds 1 or start_positions.size()) */
+struct SimulationJob {
+    std::vector<Configuration> start_positions;
+    std::vector<Configuration> target_positions;
+    bool allow_contacts = false;
+};
+
 /* simple_simulator_interface::ForwardSimulationStepTrace as filled at SPCS:1583-1595,
  * 1615-1618, 1701-1704, 1712-1715, 1776-1779.  `kinds` tags each configuration
  * with the FKS_TRACE_* push site it came from. */
@@ -401,6 +409,74 @@ class HipParticleContactSimulator {
                 r.resolver_iterations = resolver[row];
                 r.error_flags = errors[row];
             }
+        return results;
+    }
+    /* Many independent calls in one launch (fks_forward_simulate_jobs; no reference counterpart:
+     * the planner's stream of small ForwardSimulateRobots / ReverseSimulateRobots calls, whose
+     * semantics are the same, SPCS:838-841).  results[j] is what the j-th of jobs.size() plain
+     * calls issued one after the other returns, bit for bit; the jobs' particles share the
+     * device side by side. */
+    std::vector<std::vector<SimulationResult>> ForwardSimulateRobotsJobs(const RobotDescription& immutable_robot,
+                                                                         const std::vector<SimulationJob>& jobs) {
+        if (jobs.empty()) throw std::invalid_argument("a job batch needs at least one job");
+        SetRobot(immutable_robot);
+        const size_t W = (size_t)immutable_robot.ConfigurationWidth(), J = jobs.size();
+        size_t N = 0, NT = 0;
+        for (const SimulationJob& job : jobs) {
+            const size_t n = job.start_positions.size(), nt = job.target_positions.size();
+            if (n > 0 && nt != 1 && nt != n) throw std::invalid_argument("a job must hold 1 or start_positions.size() targets");
+            N += n;
+            NT += n > 0 ? nt : 0;
+        }
+        std::vector<double> s(N * W), t(NT * W), out(N * W);
+        std::vector<uint8_t> collided(N);
+        std::vector<uint32_t> micro(N), resolver(N), errors(N);
+        std::vector<fks_job> cj(J);
+        size_t at = 0, tat = 0;
+        for (size_t j = 0; j < J; ++j) {
+            const SimulationJob& job = jobs[j];
+            const size_t n = job.start_positions.size(), nt = n > 0 ? job.target_positions.size() : 0;
+            for (size_t i = 0; i < n; ++i) {
+                if (job.start_positions[i].size() != W) throw std::invalid_argument("start configuration has the wrong width");
+                std::copy(job.start_positions[i].begin(), job.start_positions[i].end(), s.begin() + (at + i) * W);
+            }
+            for (size_t i = 0; i < nt; ++i) {
+                if (job.target_positions[i].size() != W) throw std::invalid_argument("target configuration has the wrong width");
+                std::copy(job.target_positions[i].begin(), job.target_positions[i].end(), t.begin() + (tat + i) * W);
+            }
+            fks_job& c = cj[j];
+            c = fks_job();
+            c.starts = s.data() + at * W;
+            c.n = n;
+            c.targets = t.data() + tat * W;
+            c.num_targets = n > 0 ? nt : 1;
+            c.allow_contacts = job.allow_contacts ? 1 : 0;
+            c.out_positions = out.data() + at * W;
+            c.out_collided = collided.data() + at;
+            c.out_microsteps = micro.data() + at;
+            c.out_resolver_iterations = resolver.data() + at;
+            c.out_error_flags = errors.data() + at;
+            at += n;
+            tat += nt;
+        }
+        dev_.simulate_jobs(cj.data(), J, "ForwardSimulateRobotsJobs");
+        std::vector<std::vector<SimulationResult>> results(J);
+        size_t row = 0;
+        for (size_t j = 0; j < J; ++j) {
+            const SimulationJob& job = jobs[j];
+            const size_t n = job.start_positions.size();
+            results[j].resize(n);
+            for (size_t i = 0; i < n; ++i, ++row) {
+                SimulationResult& r = results[j][i];
+                r.result_config.assign(out.begin() + row * W, out.begin() + (row + 1) * W);
+                r.target_config = job.target_positions.size() == n ? job.target_positions[i] : job.target_positions[0];
+                r.did_contact = collided[row] != 0;
+                r.outcome_is_valid = true;
+                r.microsteps = micro[row];
+                r.resolver_iterations = resolver[row];
+                r.error_flags = errors[row];
+            }
+        }
         return results;
     }
     /* ReverseSimulateRobots (SPCS:806-822) == forward simulation (SPCS:838-841) */

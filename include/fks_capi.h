@@ -19,6 +19,8 @@
  *   fks_forward_simulate_device-> same as fks_forward_simulate, inputs/outputs already in HBM
  *   fks_forward_simulate_path  -> the planner's loop of ForwardSimulateRobots calls over a waypoint list
  *                                 (no single reference function), in one launch
+ *   fks_forward_simulate_jobs  -> the planner's independent ForwardSimulateRobots / ReverseSimulateRobots
+ *                                 calls (tree extensions, edge attempts, policy roll-outs), in one launch
  *   fks_check_config_collision -> SimpleParticleContactSimulator::CheckConfigCollision   (SPCS:1398-1416),
  *                                 batched (one call per configuration in the reference)
  *   fks_get_statistics         -> SimpleParticleContactSimulator::GetStatistics          (SPCS:488-500)
@@ -351,6 +353,58 @@ fks_status fks_forward_simulate_path_device(fks_context* ctx, const double* d_st
                                             uint32_t* d_out_microsteps, uint32_t* d_out_resolver_iterations,
                                             uint32_t* d_out_error_flags, void* stream, int32_t synchronize);
 
+/* Many independent calls in one launch (added within ABI 10).  A job is one plain call's
+ * arguments: its start configurations (n may be 0), its targets (num_targets == 1 or n), its
+ * allow_contacts and its own five output arrays.  first_particle_id is 0 for a whole job; a
+ * shard of a job passes its range's start, as fks_forward_simulate_device does. */
+typedef struct {
+    const double* starts;
+    uint64_t n;
+    const double* targets;
+    uint64_t num_targets; /* 1 or n */
+    uint64_t first_particle_id;
+    int32_t allow_contacts;
+    int32_t reserved;
+    double* out_positions; /* [n][W], required when n > 0 */
+    uint8_t* out_collided; /* the other four [n], each may be NULL */
+    uint32_t* out_microsteps;
+    uint32_t* out_resolver_iterations;
+    uint32_t* out_error_flags;
+} fks_job;
+#define FKS_MAX_JOBS 65536u
+/* With the context at call index c, a batch of num_jobs jobs returns byte for byte what this
+ * sequence of plain calls returns, and leaves the call index at c + num_jobs:
+ *     j = 0 .. num_jobs-1:  fks_set_call_index(c + j);
+ *                           r_j = fks_forward_simulate(starts_j, n_j, targets_j, num_targets_j, allow_contacts_j, ...)
+ * so job j draws its noise under the key of call c + j with particle ids first_particle_id_j +
+ * local, and a job's particles never interact with another job's.  The jobs' particles share
+ * the device side by side: the batch lasts about as long as one plain call over all of them.
+ * An empty job launches nothing and consumes its call index; when every job is empty the call
+ * succeeds, launches nothing and consumes num_jobs call indices.  ReverseSimulateRobots has
+ * the semantics of ForwardSimulateRobots (SPCS:838-841), so there is no reverse entry.
+ * fks_get_statistics and the work counters of fks_get_last_call_counters grow by the
+ * sequence's sums; `calls` counts 1 and `particles` the sum of n.
+ * Refused before anything is staged or counted, with the call index unchanged and the reason in
+ * fks_get_last_error: num_jobs == 0, num_jobs > FKS_MAX_JOBS (65,536), a job whose num_targets
+ * is neither 1 nor n, a job with n > 0 and a NULL starts, targets or out_positions, or a sum of
+ * n above 2^32-1 (FKS_ERR_INVALID_ARGUMENT); no robot set (FKS_ERR_NO_ROBOT); a context with
+ * fks_set_individual_jacobians on (FKS_ERR_UNSUPPORTED).
+ * Every job has a kernel-argument record (sizeof(SimArgs), 1,824 bytes) in pinned host memory and
+ * in HBM, kept by the context once grown: the 65,536 cap bounds them at about 114 MiB each.
+ * The kernel is chosen as a plain call over the sum of n would choose it: the small-batch jobs
+ * kernel (FKS_KERNEL_JOBS_SMALL_BATCH) when the sum fits small_batch_resident_waves, no
+ * segments are set, the block is not lean and fks_set_small_batch_kernel is on; the throughput
+ * jobs kernel (FKS_KERNEL_JOBS) otherwise.  fks_set_segment_steps / _policy / _heavy_relative
+ * apply as to a plain call over the sum; fks_set_cooperative_waves does not apply, and the
+ * call never builds or launches the shape-specialised module.
+ * Host buffers: every job's inputs go up in one copy and each output array comes down in one. */
+fks_status fks_forward_simulate_jobs(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs);
+/* Same with the job array on the host and every pointer in it in HBM (see
+ * fks_forward_simulate_device for stream and synchronize): rows [a, b) of a job passed with
+ * first_particle_id = a equal the same rows of the whole job. */
+fks_status fks_forward_simulate_jobs_device(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs, void* stream,
+                                            int32_t synchronize);
+
 /* CheckConfigCollision (SPCS:1398-1416) for a batch of n configurations (host
  * buffers): SetPosition(config), CheckEnvironmentCollision at threshold
  * inflation_ratio * res (SPCS:1403, 921-981) and CheckSelfCollisions at extended
@@ -489,8 +543,11 @@ typedef enum {
     FKS_KERNEL_SHAPED_SMALL_BATCH = 7, /* ABI 10: the shape-specialised module's small-batch kernel
                                           (a small batch once the robot's module is built) */
     FKS_KERNEL_PATH = 8,             /* fks_simulate_<family>[_lean]_path (fks_forward_simulate_path) */
-    FKS_KERNEL_PATH_SMALL_BATCH = 9  /* fks_simulate_<family>_path_small: a path whose batch fits the
+    FKS_KERNEL_PATH_SMALL_BATCH = 9, /* fks_simulate_<family>_path_small: a path whose batch fits the
                                         small-batch kernel's resident waves */
+    FKS_KERNEL_JOBS = 10,            /* fks_simulate_<family>[_lean]_jobs (fks_forward_simulate_jobs) */
+    FKS_KERNEL_JOBS_SMALL_BATCH = 11 /* fks_simulate_<family>_jobs_small: a job batch whose particles
+                                        together fit the small-batch kernel's resident waves */
 } fks_kernel_kind;
 /* The launch layout fks_set_robot chose (ABI 8; diagnostic, no reference counterpart). */
 typedef struct fks_launch_info {
@@ -727,6 +784,12 @@ fks_status fks_multi_forward_simulate_path(fks_multi_context* m, const double* s
                                            uint64_t num_legs, uint64_t num_targets, int32_t allow_contacts, double* out_positions,
                                            uint8_t* out_collided, uint32_t* out_microsteps, uint32_t* out_resolver_iterations,
                                            uint32_t* out_error_flags);
+/* fks_forward_simulate_jobs over the active devices: the jobs' particles laid end to end are cut
+ * into the same contiguous shards; a device gets, of every job its shard meets, the sub-range
+ * with first_particle_id = the sub-range's start within the job, and every other job empty, so
+ * every device consumes num_jobs call indices from the multi context's, which then advances by
+ * num_jobs.  Refusals as fks_forward_simulate_jobs */
+fks_status fks_multi_forward_simulate_jobs(fks_multi_context* m, const fks_job* jobs, uint64_t num_jobs);
 fks_status fks_multi_get_statistics(const fks_multi_context* m, fks_statistics* out);
 fks_status fks_multi_reset_statistics(fks_multi_context* m);
 fks_status fks_multi_get_last_call_counters(const fks_multi_context* m, fks_call_counters* out);
