@@ -221,7 +221,8 @@ class LaunchInfo(ctypes.Structure):
 
 
 KERNEL_KINDS = {0: "none", 1: "throughput", 2: "small_batch", 3: "shaped", 4: "traced", 5: "individual", 6: "cooperative",
-                7: "shaped_small_batch", 8: "path", 9: "path_small_batch", 10: "jobs", 11: "jobs_small_batch"}
+                7: "shaped_small_batch", 8: "path", 9: "path_small_batch", 10: "jobs", 11: "jobs_small_batch",
+                12: "path_jobs", 13: "path_jobs_small_batch"}
 
 
 class Job(ctypes.Structure):
@@ -230,6 +231,25 @@ class Job(ctypes.Structure):
         ("starts", c_void_p),
         ("n", c_uint64),
         ("targets", c_void_p),
+        ("num_targets", c_uint64),
+        ("first_particle_id", c_uint64),
+        ("allow_contacts", c_int32),
+        ("reserved", c_int32),
+        ("out_positions", c_void_p),
+        ("out_collided", c_void_p),
+        ("out_microsteps", c_void_p),
+        ("out_resolver_iterations", c_void_p),
+        ("out_error_flags", c_void_p),
+    ]
+
+
+class PathJob(ctypes.Structure):
+    """fks_path_job: one path call's arguments (host or device pointers, as the entry takes them)."""
+    _fields_ = [
+        ("starts", c_void_p),
+        ("n", c_uint64),
+        ("waypoints", c_void_p),
+        ("num_legs", c_uint64),
         ("num_targets", c_uint64),
         ("first_particle_id", c_uint64),
         ("allow_contacts", c_int32),
@@ -316,6 +336,8 @@ PROTOTYPES = [
     ),
     ("fks_forward_simulate_jobs", c_int32, [c_void_p, POINTER(Job), c_uint64]),
     ("fks_forward_simulate_jobs_device", c_int32, [c_void_p, POINTER(Job), c_uint64, c_void_p, c_int32]),
+    ("fks_forward_simulate_path_jobs", c_int32, [c_void_p, POINTER(PathJob), c_uint64]),
+    ("fks_forward_simulate_path_jobs_device", c_int32, [c_void_p, POINTER(PathJob), c_uint64, c_void_p, c_int32]),
     (
         "fks_forward_simulate_traced",
         c_int32,
@@ -399,6 +421,7 @@ PROTOTYPES = [
          POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)],
     ),
     ("fks_multi_forward_simulate_jobs", c_int32, [c_void_p, POINTER(Job), c_uint64]),
+    ("fks_multi_forward_simulate_path_jobs", c_int32, [c_void_p, POINTER(PathJob), c_uint64]),
     ("fks_multi_get_statistics", c_int32, [c_void_p, POINTER(Statistics)]),
     ("fks_multi_reset_statistics", c_int32, [c_void_p]),
     ("fks_multi_get_last_call_counters", c_int32, [c_void_p, POINTER(CallCounters)]),

@@ -191,5 +191,11 @@ def build_jobs_test(force: bool = False) -> str:
     return build_cpp_program(os.path.join("tests", "cpp", "jobs_interface_test.cpp"), "jobs_interface_test", force)
 
 
+def build_path_jobs_test(force: bool = False) -> str:
+    """Compile tests/cpp/path_jobs_interface_test.cpp: ForwardSimulateRobotsJobsAlongPaths against
+    the sequence of ForwardSimulateRobotsAlongPath calls on a scene built in code."""
+    return build_cpp_program(os.path.join("tests", "cpp", "path_jobs_interface_test.cpp"), "path_jobs_interface_test", force)
+
+
 if __name__ == "__main__":
     print(build_library(force=True, verbose=True))

@@ -59,6 +59,13 @@ extern "C" __global__ void fks_simulate_se3_jobs(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_linked_jobs_small(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_se2_jobs_small(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_se3_jobs_small(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_path_jobs(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_lean_path_jobs(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se2_path_jobs(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se3_path_jobs(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_path_jobs_small(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se2_path_jobs_small(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_se3_path_jobs_small(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_linked(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se2(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se3(const fksd::SimArgs* args);
@@ -138,6 +145,22 @@ sim_kernel_t jobs_small_kernel_for(int robot_type) {
         case FKS_ROBOT_SE2: return fks_simulate_se2_jobs_small;
         case FKS_ROBOT_SE3: return fks_simulate_se3_jobs_small;
         default: return fks_simulate_linked_jobs_small;
+    }
+}
+
+/* the path-job instantiations (fks_forward_simulate_path_jobs): throughput and small-batch budget */
+sim_kernel_t path_jobs_kernel_for(int robot_type, bool lean) {
+    switch (robot_type) {
+        case FKS_ROBOT_SE2: return fks_simulate_se2_path_jobs;
+        case FKS_ROBOT_SE3: return fks_simulate_se3_path_jobs;
+        default: return lean ? fks_simulate_linked_lean_path_jobs : fks_simulate_linked_path_jobs;
+    }
+}
+sim_kernel_t path_jobs_small_kernel_for(int robot_type) {
+    switch (robot_type) {
+        case FKS_ROBOT_SE2: return fks_simulate_se2_path_jobs_small;
+        case FKS_ROBOT_SE3: return fks_simulate_se3_path_jobs_small;
+        default: return fks_simulate_linked_path_jobs_small;
     }
 }
 
@@ -319,10 +342,11 @@ struct fks_context {
     fksd::SimArgs* d_args = nullptr;          /* kernel arguments, read through a pointer */
     fksd::SimArgs* h_args = nullptr;          /* pinned staging for d_args */
     fksd::SimArgs* d_path_args = nullptr;     /* a path call's records, one per leg (SimArgs.path_legs), or a job
-                                                 batch's, one per job, then its job_first (SimArgs.job_first) */
+                                                 batch's, one per job (a path-job batch's, one per job and leg), then
+                                                 its job_first (SimArgs.job_first) */
     fksd::SimArgs* h_path_args = nullptr;     /* pinned staging for d_path_args */
     size_t cap_path_args = 0;
-    std::vector<unsigned char> jobs_stage;    /* fks_forward_simulate_jobs: the jobs' inputs, then outputs, end to end */
+    std::vector<unsigned char> jobs_stage;    /* fks_forward_simulate_jobs / _path_jobs: the jobs' inputs, then outputs, end to end */
     bool pending = false;
     int pending_kind = 0; /* 0 = forward simulation, 1 = batched config check */
     hipStream_t pending_stream = nullptr;
@@ -1305,25 +1329,34 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
                                   double* d_out_positions, uint8_t* d_out_collided, uint32_t* d_out_microsteps,
                                   uint32_t* d_out_resolver_iterations, uint32_t* d_out_error_flags, void* stream,
                                   int32_t synchronize, const TraceDev* tr, double* d_pid_io = nullptr, uint64_t path_legs = 0,
-                                  const fks_job* jobs = nullptr, uint64_t num_jobs = 0) {
+                                  const fks_job* jobs = nullptr, uint64_t num_jobs = 0, const fks_path_job* pjobs = nullptr) {
     /* path_legs > 0: fks_forward_simulate_path (d_targets holds the waypoints, the outputs are
      * leg-major); jobs: fks_forward_simulate_jobs (n is the jobs' sum, the particle arguments are
-     * each job's own, already checked by jobs_arguments); neither: a plain call */
+     * each job's own, already checked by jobs_arguments); pjobs: fks_forward_simulate_path_jobs
+     * (as jobs, checked by path_jobs_arguments; every job has its own legs); none: a plain call */
     const bool path = path_legs > 0;
+    uint64_t pj_legs = 0, pj_max_legs = 0, pj_rows = 0; /* a path-job batch's legs, longest job and sum of n x legs */
+    for (uint64_t j = 0; pjobs && j < num_jobs; ++j) {
+        pj_legs += pjobs[j].num_legs;
+        pj_max_legs = std::max<uint64_t>(pj_max_legs, pjobs[j].num_legs);
+        pj_rows += pjobs[j].n * pjobs[j].num_legs;
+    }
+    /* legs of a particle's ticket space (seg_done counts legs x nseg segments) */
+    const uint64_t space_legs = path ? path_legs : (pjobs ? pj_max_legs : 1u);
     if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
     if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
-    if (!jobs && n > 0 && (!d_starts || !d_targets || !d_out_positions))
+    if (!jobs && !pjobs && n > 0 && (!d_starts || !d_targets || !d_out_positions))
         return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "null device buffer");
     if (n > 0 && num_targets != 1 && num_targets != n)
         return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "targets must be 1 or n (SPCS:792)");
     if (n > 0xffffffffull) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per call");
-    if (path) {
+    if (path || pjobs) {
         /* seg_done counts a particle's segments over all legs in 31 bits (the top bit marks a claim) */
         const uint32_t T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
         const uint32_t k = std::min(ctx->segment_steps ? ctx->segment_steps : kDefaultSegmentSteps, T);
         const bool segmented = ctx->segment_steps != 0 || n > (uint64_t)ctx->grid_waves; /* as below */
         const uint64_t nseg = segmented ? ((uint64_t)T - 1u) / k + 1u : 1u;
-        if (path_legs >= (1ull << 31) || path_legs * nseg >= (1ull << 31))
+        if (space_legs >= (1ull << 31) || space_legs * nseg >= (1ull << 31))
             return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "legs x segments per leg must stay below 2^31");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1333,10 +1366,10 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     ctx->call_start = std::chrono::steady_clock::now();
     const uint64_t first_call = ctx->call_index;
     const uint64_t key = splitmix64(ctx->seed ^ splitmix64(first_call));
-    ctx->call_index += path ? path_legs : (jobs ? num_jobs : 1u);
+    ctx->call_index += path ? path_legs : (jobs ? num_jobs : (pjobs ? pj_legs : 1u));
     std::memset(&ctx->last, 0, sizeof(ctx->last));
-    ctx->last.particles = path ? n * path_legs : n; /* a path's counters are its chain's sums */
-    if ((path || jobs) && n == 0) return FKS_OK; /* the chain's calls would launch nothing either */
+    ctx->last.particles = path ? n * path_legs : (pjobs ? pj_rows : n); /* a path's counters are its chain's sums */
+    if ((path || jobs || pjobs) && n == 0) return FKS_OK; /* the chain's calls would launch nothing either */
     fksd::SimArgs a;
     std::memset(&a, 0, sizeof(a));
     a.sdf_g = ctx->sdf_g;
@@ -1398,10 +1431,10 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
         a.seg_heavy_resolver = (uint32_t)std::min<uint64_t>(heavy, 0xffffffffull);
         a.seg_heavy_prio = ctx->heavy_priority;
         /* the relative test's running sums pack 24 bits of segments: off for larger batches */
-        a.seg_heavy_rel = ((uint64_t)n * a.nseg * (path ? path_legs : 1u) < (1ull << 24)) ? ctx->heavy_relative : 0u;
+        a.seg_heavy_rel = ((uint64_t)n * a.nseg * space_legs < (1ull << 24)) ? ctx->heavy_relative : 0u;
     }
     /* a path's segment space is path_legs x nseg, so seg_done is needed from two legs on */
-    const uint64_t segments = (uint64_t)a.nseg * (path ? path_legs : 1u);
+    const uint64_t segments = (uint64_t)a.nseg * space_legs;
     if (segments > 1 && a.nseg == 1) {
         if (n > ctx->cap_seg_done) {
             HIP_TRY(ctx, ensure(&ctx->d_seg_done, (size_t)n));
@@ -1436,16 +1469,18 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     }
     /* a batch that fits the small-batch kernel's resident waves, whole particles, plain
      * simulation: that kernel (every particle has its wave from the start either way) */
-    const bool coop = !path && !jobs && ctx->small_batch && ctx->cooperative && !tr && !ctx->individual_jacobians && !ctx->lean &&
+    const bool coop = !path && !jobs && !pjobs && ctx->small_batch && ctx->cooperative && !tr && !ctx->individual_jacobians && !ctx->lean &&
                       a.nseg == 1 && n > 0 && n <= (uint64_t)ctx->coop_particles;
     const bool small = !coop && ctx->small_batch && !tr && !ctx->individual_jacobians && !ctx->lean && a.nseg == 1 &&
                        n <= (uint64_t)ctx->small_grid_waves;
     const fksd::SimArgs* d_launch_args = ctx->d_args;
     /* a job batch's records are followed by its job_first[num_jobs + 1], in whole records */
     const size_t first_records = jobs ? ((size_t)(num_jobs + 1) * sizeof(uint32_t) + sizeof(fksd::SimArgs) - 1) / sizeof(fksd::SimArgs) : 0;
-    const size_t records = path ? (size_t)path_legs : (size_t)num_jobs + first_records;
+    /* ... and a path-job batch's, one per (job, leg), by job_first and leg_first[num_jobs + 1] */
+    const size_t pj_first_records = pjobs ? (2 * (size_t)(num_jobs + 1) * sizeof(uint32_t) + sizeof(fksd::SimArgs) - 1) / sizeof(fksd::SimArgs) : 0;
+    const size_t records = path ? (size_t)path_legs : (pjobs ? (size_t)pj_legs + pj_first_records : (size_t)num_jobs + first_records);
     /* the previous call has settled, so the pinned staging copies are free */
-    if ((path || jobs) && records > ctx->cap_path_args) {
+    if ((path || jobs || pjobs) && records > ctx->cap_path_args) {
         if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
         ctx->h_path_args = nullptr;
         ctx->cap_path_args = 0;
@@ -1453,7 +1488,55 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
         HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_path_args, records * sizeof(fksd::SimArgs), 0));
         ctx->cap_path_args = records;
     }
-    if (jobs) {
+    if (pjobs) {
+        /* job-major, one record per (job, leg): a job's records are its path's (below) with the
+         * job's own arguments, the key of the sequence's call index, and the job's slices of the
+         * segment arrays; the two prefix arrays follow the records in the same upload */
+        const uint64_t W = (uint64_t)ctx->R.W;
+        uint32_t* h_first = reinterpret_cast<uint32_t*>(ctx->h_path_args + pj_legs);
+        uint32_t* h_leg_first = h_first + num_jobs + 1;
+        a.job_first = reinterpret_cast<const uint32_t*>(ctx->d_path_args + pj_legs);
+        a.num_jobs = (uint32_t)num_jobs;
+        a.jobs_total = n;
+        a.path_legs_max = (uint32_t)pj_max_legs;
+        /* whole legs and a wave for every particle: the wave keeps its particle through its job's legs */
+        a.path_carry = (a.nseg == 1 && n <= (uint64_t)(small ? ctx->small_grid_waves : ctx->grid_waves)) ? 1u : 0u;
+        uint64_t base = 0, rec = 0;
+        for (uint64_t j = 0; j < num_jobs; ++j) {
+            const fks_path_job& job = pjobs[j];
+            h_first[j] = (uint32_t)base;
+            h_leg_first[j] = (uint32_t)rec;
+            for (uint64_t leg = 0; leg < job.num_legs; ++leg) {
+                fksd::SimArgs& r = ctx->h_path_args[rec + leg];
+                r = a;
+                const uint64_t leg_key = splitmix64(ctx->seed ^ splitmix64(first_call + rec + leg));
+                r.key0 = (uint32_t)leg_key;
+                r.key1 = (uint32_t)(leg_key >> 32);
+                r.path_legs = (uint32_t)job.num_legs;
+                r.num_targets = job.num_targets;
+                r.n = job.n;
+                r.first_pid = job.first_particle_id;
+                r.allow_contacts = job.allow_contacts ? 1 : 0;
+                r.seg_state = a.seg_state ? a.seg_state + base * a.seg_stride : nullptr;
+                r.seg_done = a.seg_done ? a.seg_done + base : nullptr;
+                r.job_base = (uint32_t)base;
+                if (job.n == 0) continue; /* never read: no particle maps to an empty job */
+                r.targets = job.waypoints + leg * job.num_targets * W;
+                r.starts = leg == 0 ? job.starts : job.out_positions + (leg - 1) * job.n * W;
+                r.out_q = job.out_positions + leg * job.n * W;
+                r.out_collided = job.out_collided ? job.out_collided + leg * job.n : nullptr;
+                r.out_micro = job.out_microsteps ? job.out_microsteps + leg * job.n : nullptr;
+                r.out_resolver = job.out_resolver_iterations ? job.out_resolver_iterations + leg * job.n : nullptr;
+                r.out_err = job.out_error_flags ? job.out_error_flags + leg * job.n : nullptr;
+            }
+            base += job.n;
+            rec += job.num_legs;
+        }
+        h_first[num_jobs] = (uint32_t)base; /* == n */
+        h_leg_first[num_jobs] = (uint32_t)rec;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path_args, ctx->h_path_args, records * sizeof(fksd::SimArgs), hipMemcpyHostToDevice, s));
+        d_launch_args = ctx->d_path_args;
+    } else if (jobs) {
         /* one record per job: the same call over all n particles except for the job's key (the
          * sequence's call index), its own arguments and outputs, and its slices of the segment
          * arrays, which start at the job's first global particle */
@@ -1524,19 +1607,20 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     /* the plain throughput path runs the robot's shape-specialised kernel: built (or fetched
      * from a cache) here at the first such launch; a failure keeps the generic kernel and is
      * reported by fks_get_specialization / fks_get_last_error, not by this call */
-    if (ctx->spec_pending && !path && !jobs && !tr && !small && !coop && !ctx->individual_jacobians) {
+    if (ctx->spec_pending && !path && !jobs && !pjobs && !tr && !small && !coop && !ctx->individual_jacobians) {
         ctx->spec_pending = false;
         const std::string keep = ctx->last_error;
         if (spec_prepare(ctx) != FKS_OK) ctx->last_error = keep + (keep.empty() ? "" : "; ") + ctx->last_error;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
     }
     /* (a path runs the generic path kernels: it neither builds nor launches the shape's module) */
-    const bool shaped = ctx->spec_fn && !path && !jobs && !tr && !small && !coop && !ctx->individual_jacobians;
+    const bool shaped = ctx->spec_fn && !path && !jobs && !pjobs && !tr && !small && !coop && !ctx->individual_jacobians;
     /* a small batch runs the shape's small-batch kernel once the robot's module is built (it is
      * never built for a small batch: robots only ever simulated in small batches cost no compile) */
-    const bool shaped_small = !path && !jobs && small && ctx->spec_fn && ctx->spec_small_fn;
+    const bool shaped_small = !path && !jobs && !pjobs && small && ctx->spec_fn && ctx->spec_small_fn;
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    ctx->last_kernel = jobs ? (small ? FKS_KERNEL_JOBS_SMALL_BATCH : FKS_KERNEL_JOBS)
+    ctx->last_kernel = pjobs ? (small ? FKS_KERNEL_PATH_JOBS_SMALL_BATCH : FKS_KERNEL_PATH_JOBS)
+                       : jobs ? (small ? FKS_KERNEL_JOBS_SMALL_BATCH : FKS_KERNEL_JOBS)
                        : path ? (small ? FKS_KERNEL_PATH_SMALL_BATCH : FKS_KERNEL_PATH)
                        : tr ? FKS_KERNEL_TRACED
                           : (shaped ? FKS_KERNEL_SHAPED
@@ -1559,6 +1643,9 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     } else if (coop) {
         hipLaunchKernelGGL(coop_kernel_for(ctx->R.type), dim3((uint32_t)n), dim3(64 * ctx->coop_waves), ctx->coop_lds_bytes, s,
                            static_cast<const fksd::SimArgs*>(ctx->d_args));
+    } else if (pjobs) {
+        hipLaunchKernelGGL(small ? path_jobs_small_kernel_for(ctx->R.type) : path_jobs_kernel_for(ctx->R.type, ctx->lean), dim3(grid),
+                           dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
     } else if (jobs) {
         hipLaunchKernelGGL(small ? jobs_small_kernel_for(ctx->R.type) : jobs_kernel_for(ctx->R.type, ctx->lean), dim3(grid),
                            dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
@@ -1968,6 +2055,145 @@ fks_status fks_forward_simulate_jobs(fks_context* ctx, const fks_job* jobs, uint
         if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations, h_res + at, job.n * sizeof(uint32_t));
         if (job.out_error_flags) std::memcpy(job.out_error_flags, h_err + at, job.n * sizeof(uint32_t));
         at += job.n;
+    }
+    ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
+    return FKS_OK;
+}
+
+}  // extern "C"
+
+/* what both path-jobs entries refuse before anything is staged or counted; *total: the sum of n,
+ * *rows: the sum of n x num_legs (the rows of a leg-major output array) */
+static fks_status path_jobs_arguments(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs, uint64_t* total, uint64_t* rows) {
+    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
+    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
+    if (num_jobs == 0 || !jobs) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "a path-job batch needs at least one job");
+    if (num_jobs > FKS_MAX_JOBS) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 65536 jobs per batch");
+    if (ctx->individual_jacobians)
+        return fail(ctx, FKS_ERR_UNSUPPORTED,
+                    "no path-jobs kernel with individual Jacobians (fks_set_individual_jacobians): issue plain calls");
+    uint64_t sum = 0, legs = 0, max_legs = 0, r = 0;
+    for (uint64_t j = 0; j < num_jobs; ++j) {
+        const fks_path_job& job = jobs[j];
+        if (job.num_legs == 0) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": a path needs at least one leg");
+        if (job.num_legs > FKS_MAX_PATH_JOB_LEGS || legs + job.num_legs > FKS_MAX_PATH_JOB_LEGS)
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 65536 legs per batch (the sum of num_legs)");
+        if (job.num_targets != 1 && job.num_targets != job.n)
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT,
+                        "job " + std::to_string(j) + ": waypoints must hold 1 or n configurations per leg (SPCS:792)");
+        if (job.n > 0 && (!job.starts || !job.waypoints || !job.out_positions))
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": null starts, waypoints or out_positions");
+        if (job.n > 0xffffffffull || sum + job.n > 0xffffffffull)
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per batch");
+        sum += job.n;
+        legs += job.num_legs;
+        max_legs = std::max(max_legs, job.num_legs);
+        r += job.n * job.num_legs; /* < 2^32 x 2^16 */
+    }
+    /* seg_done counts the longest job's legs x segments per leg in 31 bits (simulate_device's rule) */
+    const uint32_t T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
+    const uint32_t k = std::min(ctx->segment_steps ? ctx->segment_steps : kDefaultSegmentSteps, T);
+    const bool segmented = ctx->segment_steps != 0 || sum > (uint64_t)ctx->grid_waves;
+    const uint64_t nseg = segmented ? ((uint64_t)T - 1u) / k + 1u : 1u;
+    if (max_legs * nseg >= (1ull << 31)) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "legs x segments per leg must stay below 2^31");
+    *total = sum;
+    *rows = r;
+    return FKS_OK;
+}
+
+extern "C" {
+
+fks_status fks_forward_simulate_path_jobs_device(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs, void* stream,
+                                                 int32_t synchronize) {
+    uint64_t total = 0, rows = 0;
+    const fks_status st = path_jobs_arguments(ctx, jobs, num_jobs, &total, &rows);
+    if (st != FKS_OK) return st;
+    return simulate_device(ctx, nullptr, total, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, stream, synchronize,
+                           nullptr, nullptr, 0, nullptr, num_jobs, jobs);
+}
+
+fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs) {
+    uint64_t N = 0, R = 0;
+    fks_status st = path_jobs_arguments(ctx, jobs, num_jobs, &N, &R);
+    if (st != FKS_OK) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = settle(ctx);
+    if (st != FKS_OK) return st;
+    if (N == 0) return simulate_device(ctx, nullptr, 0, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1,
+                                       nullptr, nullptr, 0, nullptr, num_jobs, jobs);
+    /* the staging buffers of the plain host calls: d_starts holds every job's starts and then
+     * every job's waypoints, so the inputs go up in one copy; the outputs are the jobs' leg-major
+     * blocks one behind the other (R = sum of n x num_legs rows) */
+    const size_t W = (size_t)ctx->R.W;
+    uint64_t NT = 0;
+    for (uint64_t j = 0; j < num_jobs; ++j) NT += jobs[j].n > 0 ? jobs[j].num_targets * jobs[j].num_legs : 0;
+    const uint64_t rows = std::max(N + NT, R);
+    if (rows > ctx->cap_particles) {
+        HIP_TRY(ctx, ensure(&ctx->d_starts, rows * W));
+        HIP_TRY(ctx, ensure(&ctx->d_out, rows * W));
+        HIP_TRY(ctx, ensure(&ctx->d_coll, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_micro, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_res, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_err, rows));
+        ctx->cap_particles = rows;
+    }
+    const size_t in_bytes = (N + NT) * W * sizeof(double);
+    const size_t q_bytes = R * W * sizeof(double), u_bytes = R * sizeof(uint32_t);
+    ctx->jobs_stage.resize(std::max(in_bytes, q_bytes + 3 * u_bytes + R));
+    double* h_in = reinterpret_cast<double*>(ctx->jobs_stage.data());
+    std::vector<fks_path_job> dev(jobs, jobs + num_jobs); /* the same jobs over the staging buffers */
+    uint64_t at = 0, tat = N, oat = 0;
+    for (uint64_t j = 0; j < num_jobs; ++j) {
+        fks_path_job& d = dev[j];
+        if (d.n == 0) continue;
+        const uint64_t nt = d.num_targets * d.num_legs;
+        std::memcpy(h_in + at * W, d.starts, d.n * W * sizeof(double));
+        std::memcpy(h_in + tat * W, d.waypoints, nt * W * sizeof(double));
+        d.starts = ctx->d_starts + at * W;
+        d.waypoints = ctx->d_starts + tat * W;
+        d.out_positions = ctx->d_out + oat * W;
+        d.out_collided = ctx->d_coll + oat;
+        d.out_microsteps = ctx->d_micro + oat;
+        d.out_resolver_iterations = ctx->d_res + oat;
+        d.out_error_flags = ctx->d_err + oat;
+        at += d.n;
+        tat += nt;
+        oat += d.n * d.num_legs;
+    }
+    HIP_TRY(ctx, hipMemcpy(ctx->d_starts, h_in, in_bytes, hipMemcpyHostToDevice));
+    st = simulate_device(ctx, nullptr, N, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, 0,
+                         nullptr, num_jobs, dev.data());
+    if (st != FKS_OK) return st;
+    /* one copy down per output array, then each job's leg-major block to its own arrays */
+    double* h_q = reinterpret_cast<double*>(ctx->jobs_stage.data());
+    uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + R * W);
+    uint32_t* h_res = h_micro + R;
+    uint32_t* h_err = h_res + R;
+    uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + R);
+    bool want_coll = false, want_micro = false, want_res = false, want_err = false;
+    for (uint64_t j = 0; j < num_jobs; ++j) {
+        if (jobs[j].n == 0) continue;
+        want_coll |= jobs[j].out_collided != nullptr;
+        want_micro |= jobs[j].out_microsteps != nullptr;
+        want_res |= jobs[j].out_resolver_iterations != nullptr;
+        want_err |= jobs[j].out_error_flags != nullptr;
+    }
+    HIP_TRY(ctx, hipMemcpy(h_q, ctx->d_out, q_bytes, hipMemcpyDeviceToHost));
+    if (want_coll) HIP_TRY(ctx, hipMemcpy(h_coll, ctx->d_coll, R, hipMemcpyDeviceToHost));
+    if (want_micro) HIP_TRY(ctx, hipMemcpy(h_micro, ctx->d_micro, u_bytes, hipMemcpyDeviceToHost));
+    if (want_res) HIP_TRY(ctx, hipMemcpy(h_res, ctx->d_res, u_bytes, hipMemcpyDeviceToHost));
+    if (want_err) HIP_TRY(ctx, hipMemcpy(h_err, ctx->d_err, u_bytes, hipMemcpyDeviceToHost));
+    oat = 0;
+    for (uint64_t j = 0; j < num_jobs; ++j) {
+        const fks_path_job& job = jobs[j];
+        if (job.n == 0) continue;
+        const uint64_t r = job.n * job.num_legs;
+        std::memcpy(job.out_positions, h_q + oat * W, r * W * sizeof(double));
+        if (job.out_collided) std::memcpy(job.out_collided, h_coll + oat, r);
+        if (job.out_microsteps) std::memcpy(job.out_microsteps, h_micro + oat, r * sizeof(uint32_t));
+        if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations, h_res + oat, r * sizeof(uint32_t));
+        if (job.out_error_flags) std::memcpy(job.out_error_flags, h_err + oat, r * sizeof(uint32_t));
+        oat += r;
     }
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
     return FKS_OK;

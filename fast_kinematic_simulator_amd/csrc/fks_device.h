@@ -371,7 +371,7 @@ struct SimArgs {
     double* scratch;
     uint64_t scratch_per_wave; /* doubles */
     uint32_t row_cap;          /* 3 * P */
-    uint32_t pad2;
+    uint32_t path_legs_max;    /* path-job batches: the longest job's legs (below); 0 otherwise */
     LdsLayout L;               /* per-wave LDS carve-out */
     ScratchLayout SL;          /* per-wave scratch carve-out */
     double self_res;           /* batched CheckConfigCollision: extended-cell size (SPCS:1404) */
@@ -403,6 +403,14 @@ struct SimArgs {
      * ticket space is one plain call's over jobs_total = sum of n particles; job_first
      * [num_jobs + 1] holds the jobs' first global particles (job_first[num_jobs] ==
      * jobs_total; empty jobs make equal neighbours) and job_base is the record's own entry */
+    /* path-job batches (fks_forward_simulate_path_jobs, the *_path_jobs kernels): both of the
+     * above.  The records are job-major, one per (job, leg): leg k of job j is record
+     * leg_first[j] + k, where leg_first[num_jobs + 1] is stored right behind job_first
+     * (job_first[num_jobs + 1 + j]).  A job's records are its path's (path_legs is the job's own
+     * number of legs, starts of leg k >= 1 the job's output slice of leg k - 1) with the job's
+     * job_base and slices of seg_state / seg_done.  The ticket space is one path's over
+     * jobs_total particles and path_legs_max x nseg segments; a particle of a shorter job rests
+     * at seg_done == its own path_legs x nseg, and the ticket of that segment is dropped */
     const uint32_t* job_first;
     uint32_t num_jobs;
     uint32_t job_base;

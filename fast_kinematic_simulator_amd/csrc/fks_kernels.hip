@@ -3924,7 +3924,11 @@ __device__ __forceinline__ uint32_t job_of(const SimArgs* __restrict__ args, uin
  * JOBS: the job-batch kernels (fks_forward_simulate_jobs).  args is an array of A.num_jobs
  * records, one per job (SimArgs.job_first), and the ticket space is that of one plain call
  * over the jobs' particles laid end to end: ticket t is segment t / jobs_total of global
- * particle t % jobs_total, which job_of() maps to its job's record */
+ * particle t % jobs_total, which job_of() maps to its job's record.
+ * PATH && JOBS: the path-job kernels (fks_forward_simulate_path_jobs).  args is job-major, one
+ * record per (job, leg): leg k of job j is record leg_first[j] + k, with leg_first[num_jobs + 1]
+ * stored behind job_first.  The ticket space is one path's over all jobs' particles, as long
+ * as the longest job's (SimArgs.path_legs_max); a record's path_legs is its own job's */
 template <int RT, bool TR, bool IND = false, bool LEAN = false, int COOP = 0, bool PATH = false, bool JOBS = false>
 __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ args, double* lds_mem) {
     const SimArgs& A = *args;
@@ -3991,7 +3995,8 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
     unsigned long long* next_particle = reinterpret_cast<unsigned long long*>(s.lds() + LAY(*s.A).misc + 31);
     uint32_t* seg_seen = reinterpret_cast<uint32_t*>(s.lds() + LAY(*s.A).misc + 30);
     const uint32_t nseg = A.nseg;
-    const uint32_t nsegs = PATH ? nseg * A.path_legs : nseg; /* segments per particle (seg_done counts these) */
+    /* segments per particle (seg_done counts these); of the longest job in a path-job batch */
+    const uint32_t nsegs = (PATH && JOBS) ? nseg * A.path_legs_max : (PATH ? nseg * A.path_legs : nseg);
     uint64_t carry = kNoTicket; /* the next segment of the particle just run, claimed by this wave */
     bool carry_heavy = false;   /* ... and whether the segment just run was contact-heavy */
     /* call counters are summed per wave and flushed once when the queue is drained
@@ -4092,8 +4097,19 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
         }
         /* from here to the end of the segment A is the leg's record: its key, targets, start
          * configurations and output slices (the plain kernels have one record) */
-        if constexpr (JOBS) leg = job_of(args, (uint32_t)global, ln);
-        const SimArgs& A = (PATH || JOBS) ? args[leg] : *args;
+        uint32_t rec = leg; /* the record's index: the leg, the job, or the job's first record + leg */
+        if constexpr (JOBS) rec = job_of(args, (uint32_t)global, ln);
+        if constexpr (PATH && JOBS) {
+            /* leg_first[job]; through readfirstlane, so that the record keeps being read with
+             * scalar loads (a loaded index would put its address, and every field, in VGPRs) */
+            rec = (uint32_t)__builtin_amdgcn_readfirstlane((int)args->job_first[args->num_jobs + 1u + rec]);
+            /* a shorter job's particle rests at seg_done == its own legs x nseg, so the ticket of
+             * that very segment passed the claim test: there is nothing to run, and record
+             * rec + leg is not this job's.  Nothing has been read, written or counted yet */
+            if (leg >= args[rec].path_legs) continue;
+            rec += leg;
+        }
+        const SimArgs& A = (PATH || JOBS) ? args[rec] : *args;
         if constexpr (PATH || JOBS) s.A = &A;
         /* the particle within its call: a job's records index their own arrays */
         const uint64_t local = JOBS ? global - A.job_base : global;
@@ -4281,7 +4297,10 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
                 bool more = !ended; /* the particle has a further segment */
                 if constexpr (PATH) {
                     nv = (uint32_t)next_seg;
-                    more = nv < nsegs;
+                    if constexpr (JOBS)
+                        more = nv < nseg * A.path_legs; /* the job's own last leg, not the batch's */
+                    else
+                        more = nv < nsegs;
                 }
                 __hip_atomic_store(A.seg_done + local, nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 publish_fence(); /* the store is visible before the ticket counter is read (Dekker with the holder) */
@@ -4522,6 +4541,39 @@ extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_jobs_small(co
 extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_jobs_small(const SimArgs* __restrict__ args) {
     extern __shared__ __attribute__((aligned(16))) double lds_mem[];
     simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, false, true>(args, lds_mem);
+}
+
+/* path-job batches (fks_forward_simulate_path_jobs): PATH && JOBS instantiations at the throughput
+ * budget ... */
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_path_jobs(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_path_jobs(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, true, 0, true, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_path_jobs(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_path_jobs(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true, true>(args, lds_mem);
+}
+/* ... and at the small-batch budget, for batches whose jobs together fit its resident waves: a
+ * wave carries its particle through its own job's legs */
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_linked_path_jobs_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_path_jobs_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true, true>(args, lds_mem);
+}
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_path_jobs_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true, true>(args, lds_mem);
 }
 
 extern "C" __global__ void FKS_KERNEL_ATTRS fks_check_configs_linked(const SimArgs* __restrict__ args) {

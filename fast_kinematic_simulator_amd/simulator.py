@@ -283,6 +283,19 @@ class HipParticleContactSimulator:
         _capi.check(st, self._ctx, "fks_forward_simulate_jobs")
         return [_job_result(r) for r in results]
 
+    def forward_simulate_path_jobs_arrays(self, robot: RobotDescription, jobs) -> list:
+        """Many independent waypoint paths in one launch (fks_forward_simulate_path_jobs).  jobs: a
+        sequence of (starts (n, W), waypoints (K, 1 or n, W), allow_contacts); the jobs may differ
+        in K.  Returns a list of the dicts forward_simulate_path_arrays returns ([K, n, ...]
+        arrays): job j is what forward_simulate_path_arrays returns at call index
+        get_call_index() + K_0 + ... + K_{j-1}, byte for byte; the call index advances by the sum
+        of K."""
+        self.set_robot(robot)
+        array, results, _keep = _host_path_jobs(jobs, robot.config_width)
+        st = self._lib.fks_forward_simulate_path_jobs(self._ctx, array, len(results))
+        _capi.check(st, self._ctx, "fks_forward_simulate_path_jobs")
+        return [_job_result(r) for r in results]
+
     def forward_simulate_mutable_arrays(self, robot: RobotDescription, start_positions, target_positions, allow_contacts: bool,
                                         controller_state) -> dict:
         """ForwardSimulateMutableRobot (SPCS:843-919) for a batch (fks_forward_simulate_mutable):
@@ -557,6 +570,24 @@ class HipParticleContactSimulator:
                                                         1 if synchronize else 0)
         _capi.check(st, self._ctx, "fks_forward_simulate_jobs_device")
 
+    def forward_simulate_path_jobs_device(self, robot: RobotDescription, jobs, stream=0, synchronize=False):
+        """fks_forward_simulate_path_jobs_device: jobs is a sequence of dicts with the fields of
+        fks_path_job (d_starts, n, d_waypoints, num_legs, num_targets, allow_contacts,
+        d_out_positions and optionally first_particle_id, d_out_collided, d_out_microsteps,
+        d_out_resolver_iterations, d_out_error_flags), every buffer a device pointer (int) as in
+        forward_simulate_device; the outputs are leg-major with the job's own n as leg stride."""
+        self.set_robot(robot)
+        array = (_capi.PathJob * max(len(jobs), 1))()
+        for j, job in enumerate(jobs):
+            array[j] = _capi.PathJob(
+                job["d_starts"] or None, int(job["n"]), job["d_waypoints"] or None, int(job["num_legs"]), int(job["num_targets"]),
+                int(job.get("first_particle_id", 0)), 1 if job["allow_contacts"] else 0, 0, job["d_out_positions"] or None,
+                job.get("d_out_collided") or None, job.get("d_out_microsteps") or None,
+                job.get("d_out_resolver_iterations") or None, job.get("d_out_error_flags") or None)
+        st = self._lib.fks_forward_simulate_path_jobs_device(self._ctx, array, len(jobs), ctypes.c_void_p(stream or None),
+                                                             1 if synchronize else 0)
+        _capi.check(st, self._ctx, "fks_forward_simulate_path_jobs_device")
+
 
 def _host_jobs(jobs, W: int):
     """The fks_job array of (starts, targets, allow_contacts) jobs over host arrays: the ctypes
@@ -576,6 +607,27 @@ def _host_jobs(jobs, W: int):
                              ptr(out["resolver_iterations"]), ptr(out["error_flags"]))
         results.append(out)
         keep.append((starts, targets))
+    return array, results, keep
+
+
+def _host_path_jobs(jobs, W: int):
+    """The fks_path_job array of (starts, waypoints, allow_contacts) jobs over host arrays: the
+    ctypes array, per job its leg-major output arrays, and the input arrays to keep alive."""
+    array = (_capi.PathJob * max(len(jobs), 1))()
+    results, keep = [], []
+    for j, (start_positions, waypoints, allow_contacts) in enumerate(jobs):
+        starts = np.ascontiguousarray(np.asarray(start_positions, dtype=np.float64).reshape(-1, W))
+        n = starts.shape[0]
+        way, K, nt = _path_waypoints(waypoints, W, n)
+        out = {"positions": np.zeros((K, n, W), dtype=np.float64), "collided": np.zeros((K, n), dtype=np.uint8),
+               "microsteps": np.zeros((K, n), dtype=np.uint32), "resolver_iterations": np.zeros((K, n), dtype=np.uint32),
+               "error_flags": np.zeros((K, n), dtype=np.uint32)}
+        ptr = (lambda a: a.ctypes.data) if n > 0 and K > 0 else (lambda a: None)
+        array[j] = _capi.PathJob(ptr(starts), n, way.ctypes.data if way.size else None, K, nt, 0, 1 if allow_contacts else 0, 0,
+                                 ptr(out["positions"]), ptr(out["collided"]), ptr(out["microsteps"]),
+                                 ptr(out["resolver_iterations"]), ptr(out["error_flags"]))
+        results.append(out)
+        keep.append((starts, way))
     return array, results, keep
 
 
@@ -711,6 +763,16 @@ class MultiDeviceSimulator:
         array, results, _keep = _host_jobs(jobs, robot.config_width)
         st = self._lib.fks_multi_forward_simulate_jobs(self._ctx, array, len(results))
         self._check(st, "fks_multi_forward_simulate_jobs")
+        return [_job_result(r) for r in results]
+
+    def forward_simulate_path_jobs_arrays(self, robot: RobotDescription, jobs) -> list:
+        """fks_multi_forward_simulate_path_jobs: HipParticleContactSimulator.forward_simulate_path_jobs_arrays
+        with the jobs' particles, laid end to end, sharded over the devices (bit-identical to one
+        device)."""
+        self.set_robot(robot)
+        array, results, _keep = _host_path_jobs(jobs, robot.config_width)
+        st = self._lib.fks_multi_forward_simulate_path_jobs(self._ctx, array, len(results))
+        self._check(st, "fks_multi_forward_simulate_path_jobs")
         return [_job_result(r) for r in results]
 
     def check_config_collisions(self, robot: RobotDescription, configs, inflation_ratio: float):

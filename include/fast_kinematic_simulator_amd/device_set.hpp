@@ -192,6 +192,27 @@ class DeviceSet {
         Check(fks_forward_simulate_jobs(ctx_, jobs, num_jobs), ctx_, what);
     }
 
+    /* many independent waypoint paths in one launch per device (fks_forward_simulate_path_jobs,
+     * host buffers); the devices are chosen from the jobs' particles together as for simulate() */
+    void simulate_path_jobs(const fks_path_job* jobs, uint64_t num_jobs, const char* what) {
+        uint64_t n = 0, legs = 0;
+        for (uint64_t j = 0; j < num_jobs; ++j) {
+            n += jobs[j].n;
+            legs += jobs[j].num_legs;
+        }
+        last_devices_ = devices_for(n);
+        if (last_devices_ >= 2) {
+            /* every device uses the call indices devices[0] would have used */
+            const uint64_t call = fks_get_call_index(ctx_);
+            MultiCheck(fks_multi_set_active_devices(multi_.get(), last_devices_), what);
+            MultiCheck(fks_multi_set_call_index(multi_.get(), call), what);
+            MultiCheck(fks_multi_forward_simulate_path_jobs(multi_.get(), jobs, num_jobs), what);
+            Check(fks_set_call_index(ctx_, call + legs), ctx_, what);
+            return;
+        }
+        Check(fks_forward_simulate_path_jobs(ctx_, jobs, num_jobs), ctx_, what);
+    }
+
     /* batched CheckConfigCollision (SPCS:1398-1416) */
     void check_configs(const double* configs, uint64_t n, double inflation_ratio, uint8_t* out_collided, uint32_t* out_error_flags,
                        const char* what) const {

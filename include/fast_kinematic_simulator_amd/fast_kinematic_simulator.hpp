@@ -360,6 +360,89 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
         }
         return out;
     }
+    /* Not part of SimulatorInterface: many independent waypoint paths in one launch
+     * (fks_forward_simulate_path_jobs), for a planner iteration's edges, each simulated forward to
+     * its target and back to the parent state (ForwardSimulateRobots then ReverseSimulateRobots,
+     * SPCS:788-822).  A job is one ForwardSimulateRobotsAlongPath call's arguments, and jobs may
+     * differ in their number of legs; results[j][k][i] is what the j-th of jobs.size() such calls
+     * issued one after the other returns for leg k and particle i, bit for bit. */
+    struct SimulationPathJob {
+        std::vector<Configuration, ConfigAlloc> start_positions;
+        std::vector<std::vector<Configuration, ConfigAlloc>> waypoints; /* [leg][1 or start_positions.size()] */
+        bool allow_contacts = false;
+    };
+    std::vector<std::vector<std::vector<SimulationResult>>> ForwardSimulateRobotsJobsAlongPaths(
+        const std::shared_ptr<BaseRobotType>& immutable_robot, const std::vector<SimulationPathJob>& jobs) {
+        if (jobs.empty()) throw std::invalid_argument("a job batch needs at least one job");
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        SetRobot(robot);
+        const size_t J = jobs.size();
+        std::vector<double> s, t;
+        std::vector<size_t> ns(J), nts(J), Ks(J);
+        size_t N = 0, R = 0;
+        for (size_t j = 0; j < J; ++j) {
+            const SimulationPathJob& job = jobs[j];
+            if (job.waypoints.empty()) throw std::invalid_argument("a path needs at least one leg");
+            const size_t n = job.start_positions.size(), nt = job.waypoints[0].size();
+            if (n > 0 && nt != 1 && nt != n) throw std::invalid_argument("every leg must hold 1 or start_positions.size() waypoints (SPCS:792)");
+            ns[j] = n;
+            nts[j] = n > 0 ? nt : 0;
+            Ks[j] = job.waypoints.size();
+            N += n;
+            R += n * Ks[j];
+            for (const auto& c : job.start_positions) {
+                const std::vector<double> f = robot.ToFlat(c);
+                s.insert(s.end(), f.begin(), f.end());
+            }
+            for (const auto& leg : job.waypoints) {
+                if (leg.size() != nt) throw std::invalid_argument("every leg must hold the same number of waypoints");
+                for (size_t i = 0; i < nts[j]; ++i) {
+                    const std::vector<double> f = robot.ToFlat(leg[i]);
+                    t.insert(t.end(), f.begin(), f.end());
+                }
+            }
+        }
+        const size_t W = N ? s.size() / N : 0;
+        std::vector<double> q(R * W);
+        std::vector<uint8_t> collided(R);
+        last_micro_.assign(R, 0);
+        last_resolver_.assign(R, 0);
+        last_errors_.assign(R, 0);
+        std::vector<fks_path_job> cj(J);
+        size_t at = 0, tat = 0, oat = 0;
+        for (size_t j = 0; j < J; ++j) {
+            fks_path_job& c = cj[j];
+            c = fks_path_job();
+            c.starts = s.data() + at * W;
+            c.n = ns[j];
+            c.waypoints = t.data() + tat * W;
+            c.num_legs = Ks[j];
+            c.num_targets = ns[j] > 0 ? nts[j] : 1;
+            c.allow_contacts = jobs[j].allow_contacts ? 1 : 0;
+            c.out_positions = q.data() + oat * W;
+            c.out_collided = collided.data() + oat;
+            c.out_microsteps = last_micro_.data() + oat;
+            c.out_resolver_iterations = last_resolver_.data() + oat;
+            c.out_error_flags = last_errors_.data() + oat;
+            at += ns[j];
+            tat += nts[j] * Ks[j];
+            oat += ns[j] * Ks[j];
+        }
+        dev_->simulate_path_jobs(cj.data(), J, "ForwardSimulateRobotsJobsAlongPaths");
+        std::vector<std::vector<std::vector<SimulationResult>>> out(J);
+        size_t row = 0;
+        for (size_t j = 0; j < J; ++j) {
+            out[j].resize(Ks[j]);
+            for (size_t k = 0; k < Ks[j]; ++k) {
+                out[j][k].reserve(ns[j]);
+                for (size_t i = 0; i < ns[j]; ++i, ++row)
+                    out[j][k].emplace_back(robot.FromFlat(q.data() + row * W),
+                                           nts[j] == ns[j] ? jobs[j].waypoints[k][i] : jobs[j].waypoints[k][0], collided[row] != 0,
+                                           true);
+            }
+        }
+        return out;
+    }
     /* SPCS:824-829: a clone reset to the start (controllers zeroed) */
     SimulationResult ForwardSimulateRobot(const std::shared_ptr<BaseRobotType>& immutable_robot, const Configuration& start_position,
                                           const Configuration& target_position, const bool allow_contacts,

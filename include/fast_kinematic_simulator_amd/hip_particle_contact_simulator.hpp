@@ -66,6 +66,15 @@ struct SimulationJob {
     bool allow_contacts = false;
 };
 
+/* One of the independent paths of ForwardSimulateRobotsJobsAlongPaths: the arguments of one
+ * ForwardSimulateRobotsAlongPath call (waypoints[leg] holds 1 or start_positions.size(), the
+ * same count for every leg of the job; jobs may differ in their number of legs) */
+struct SimulationPathJob {
+    std::vector<Configuration> start_positions;
+    std::vector<std::vector<Configuration>> waypoints;
+    bool allow_contacts = false;
+};
+
 /* simple_simulator_interface::ForwardSimulationStepTrace as filled at SPCS:1583-1595,
  * 1615-1618, 1701-1704, 1712-1715, 1776-1779.  `kinds` tags each configuration
  * with the FKS_TRACE_* push site it came from. */
@@ -476,6 +485,82 @@ class HipParticleContactSimulator {
                 r.resolver_iterations = resolver[row];
                 r.error_flags = errors[row];
             }
+        }
+        return results;
+    }
+    /* Many independent waypoint paths in one launch (fks_forward_simulate_path_jobs; no reference
+     * counterpart: a planner iteration's edges, each simulated forward to its target and back,
+     * ForwardSimulateRobots then ReverseSimulateRobots, SPCS:788-822).  results[j][k][i] is what
+     * the j-th of jobs.size() ForwardSimulateRobotsAlongPath calls issued one after the other
+     * returns for leg k and particle i, bit for bit; the jobs may differ in their number of legs. */
+    std::vector<std::vector<std::vector<SimulationResult>>> ForwardSimulateRobotsJobsAlongPaths(
+        const RobotDescription& immutable_robot, const std::vector<SimulationPathJob>& jobs) {
+        if (jobs.empty()) throw std::invalid_argument("a job batch needs at least one job");
+        SetRobot(immutable_robot);
+        const size_t W = (size_t)immutable_robot.ConfigurationWidth(), J = jobs.size();
+        size_t N = 0, NT = 0, R = 0;
+        for (const SimulationPathJob& job : jobs) {
+            if (job.waypoints.empty()) throw std::invalid_argument("a path needs at least one leg");
+            const size_t n = job.start_positions.size(), nt = job.waypoints[0].size(), K = job.waypoints.size();
+            if (n > 0 && nt != 1 && nt != n) throw std::invalid_argument("every leg must hold 1 or start_positions.size() waypoints");
+            for (const auto& leg : job.waypoints)
+                if (leg.size() != nt) throw std::invalid_argument("every leg must hold the same number of waypoints");
+            N += n;
+            NT += n > 0 ? nt * K : 0;
+            R += n * K;
+        }
+        std::vector<double> s(N * W), t(NT * W), out(R * W);
+        std::vector<uint8_t> collided(R);
+        std::vector<uint32_t> micro(R), resolver(R), errors(R);
+        std::vector<fks_path_job> cj(J);
+        size_t at = 0, tat = 0, oat = 0;
+        for (size_t j = 0; j < J; ++j) {
+            const SimulationPathJob& job = jobs[j];
+            const size_t n = job.start_positions.size(), K = job.waypoints.size(), nt = n > 0 ? job.waypoints[0].size() : 0;
+            for (size_t i = 0; i < n; ++i) {
+                if (job.start_positions[i].size() != W) throw std::invalid_argument("start configuration has the wrong width");
+                std::copy(job.start_positions[i].begin(), job.start_positions[i].end(), s.begin() + (at + i) * W);
+            }
+            for (size_t k = 0; k < K; ++k)
+                for (size_t i = 0; i < nt; ++i) {
+                    if (job.waypoints[k][i].size() != W) throw std::invalid_argument("waypoint configuration has the wrong width");
+                    std::copy(job.waypoints[k][i].begin(), job.waypoints[k][i].end(), t.begin() + (tat + k * nt + i) * W);
+                }
+            fks_path_job& c = cj[j];
+            c = fks_path_job();
+            c.starts = s.data() + at * W;
+            c.n = n;
+            c.waypoints = t.data() + tat * W;
+            c.num_legs = K;
+            c.num_targets = n > 0 ? nt : 1;
+            c.allow_contacts = job.allow_contacts ? 1 : 0;
+            c.out_positions = out.data() + oat * W;
+            c.out_collided = collided.data() + oat;
+            c.out_microsteps = micro.data() + oat;
+            c.out_resolver_iterations = resolver.data() + oat;
+            c.out_error_flags = errors.data() + oat;
+            at += n;
+            tat += nt * K;
+            oat += n * K;
+        }
+        dev_.simulate_path_jobs(cj.data(), J, "ForwardSimulateRobotsJobsAlongPaths");
+        std::vector<std::vector<std::vector<SimulationResult>>> results(J);
+        size_t row = 0;
+        for (size_t j = 0; j < J; ++j) {
+            const SimulationPathJob& job = jobs[j];
+            const size_t n = job.start_positions.size(), K = job.waypoints.size();
+            results[j].assign(K, std::vector<SimulationResult>(n));
+            for (size_t k = 0; k < K; ++k)
+                for (size_t i = 0; i < n; ++i, ++row) {
+                    SimulationResult& r = results[j][k][i];
+                    r.result_config.assign(out.begin() + row * W, out.begin() + (row + 1) * W);
+                    r.target_config = job.waypoints[k].size() == n ? job.waypoints[k][i] : job.waypoints[k][0];
+                    r.did_contact = collided[row] != 0;
+                    r.outcome_is_valid = true;
+                    r.microsteps = micro[row];
+                    r.resolver_iterations = resolver[row];
+                    r.error_flags = errors[row];
+                }
         }
         return results;
     }

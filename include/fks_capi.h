@@ -405,6 +405,62 @@ fks_status fks_forward_simulate_jobs(fks_context* ctx, const fks_job* jobs, uint
 fks_status fks_forward_simulate_jobs_device(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs, void* stream,
                                             int32_t synchronize);
 
+/* Many independent waypoint paths in one launch (added within ABI 10).  A path job is one
+ * fks_forward_simulate_path call's arguments: its start configurations (n may be 0), its
+ * waypoints, its own number of legs (jobs may differ in length), its allow_contacts and its own
+ * five leg-major output arrays.  first_particle_id is 0 for a whole job; a shard of a job passes
+ * its range's start, and the shard's own n is its leg stride. */
+typedef struct {
+    const double* starts;       /* [n][W] */
+    uint64_t n;                 /* may be 0 */
+    const double* waypoints;    /* [num_legs][num_targets][W] */
+    uint64_t num_legs;          /* >= 1 */
+    uint64_t num_targets;       /* 1 or n, for every leg */
+    uint64_t first_particle_id; /* 0 for a whole job; a shard passes its range's start */
+    int32_t allow_contacts;
+    int32_t reserved;
+    double* out_positions; /* [num_legs][n][W], required when n > 0 */
+    uint8_t* out_collided; /* the other four [num_legs][n], each may be NULL */
+    uint32_t* out_microsteps;
+    uint32_t* out_resolver_iterations;
+    uint32_t* out_error_flags;
+} fks_path_job;
+/* the sum of num_legs over a batch: one kernel-argument record per (job, leg), so the records'
+ * pinned and HBM staging keeps the bound of FKS_MAX_JOBS (about 114 MiB each) */
+#define FKS_MAX_PATH_JOB_LEGS FKS_MAX_JOBS
+/* With the context at call index c and K_j = jobs[j].num_legs, a batch returns byte for byte what
+ * this sequence of path calls returns, and leaves the call index at c + K_0 + ... + K_{J-1}:
+ *     j = 0 .. num_jobs-1:  fks_set_call_index(c + K_0 + ... + K_{j-1});
+ *                           fks_forward_simulate_path(starts_j, n_j, waypoints_j, K_j, num_targets_j, allow_contacts_j, ...)
+ * so leg k of job j draws its noise under the key of call c + K_0 + ... + K_{j-1} + k with
+ * particle ids first_particle_id_j + local, and every leg begins with ResetPosition of what the
+ * leg before returned (fks_forward_simulate_path).  With every K_j == 1 the call returns what
+ * fks_forward_simulate_jobs returns, with one job what fks_forward_simulate_path returns.
+ * An empty job launches nothing and consumes its K_j call indices; when every job is empty the
+ * call succeeds, launches nothing and consumes them all.  fks_get_statistics and the work
+ * counters of fks_get_last_call_counters grow by the sequence's sums; `calls` counts 1 and
+ * `particles` the sum of n_j x K_j.
+ * Refused before anything is staged or counted, with the call index unchanged and the reason in
+ * fks_get_last_error: num_jobs == 0, num_jobs > FKS_MAX_JOBS, a job with num_legs == 0, a sum of
+ * num_legs above FKS_MAX_PATH_JOB_LEGS, a job whose num_targets is neither 1 nor n, a job with
+ * n > 0 and a NULL starts, waypoints or out_positions, a sum of n above 2^32-1, or the longest
+ * job's legs x segments per leg >= 2^31 (FKS_ERR_INVALID_ARGUMENT); no robot set
+ * (FKS_ERR_NO_ROBOT); a context with fks_set_individual_jacobians on (FKS_ERR_UNSUPPORTED).
+ * The kernel is chosen as a plain call over the sum of n would choose it: the small-batch kernel
+ * (FKS_KERNEL_PATH_JOBS_SMALL_BATCH) when the sum fits small_batch_resident_waves, no segments
+ * are set, the block is not lean and fks_set_small_batch_kernel is on; the throughput kernel
+ * (FKS_KERNEL_PATH_JOBS) otherwise.  fks_set_segment_steps / _policy / _heavy_relative apply as
+ * to a plain call over the sum; fks_set_cooperative_waves does not apply, and the call never
+ * builds or launches the shape-specialised module.
+ * Host buffers: every job's starts and waypoints go up in one copy and each output array comes
+ * down in one. */
+fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs);
+/* Same with the job array on the host and every pointer in it in HBM (see
+ * fks_forward_simulate_device for stream and synchronize): rows [a, b) of a job passed with
+ * first_particle_id = a equal the same rows of the whole job. */
+fks_status fks_forward_simulate_path_jobs_device(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs, void* stream,
+                                                 int32_t synchronize);
+
 /* CheckConfigCollision (SPCS:1398-1416) for a batch of n configurations (host
  * buffers): SetPosition(config), CheckEnvironmentCollision at threshold
  * inflation_ratio * res (SPCS:1403, 921-981) and CheckSelfCollisions at extended
@@ -546,8 +602,11 @@ typedef enum {
     FKS_KERNEL_PATH_SMALL_BATCH = 9, /* fks_simulate_<family>_path_small: a path whose batch fits the
                                         small-batch kernel's resident waves */
     FKS_KERNEL_JOBS = 10,            /* fks_simulate_<family>[_lean]_jobs (fks_forward_simulate_jobs) */
-    FKS_KERNEL_JOBS_SMALL_BATCH = 11 /* fks_simulate_<family>_jobs_small: a job batch whose particles
-                                        together fit the small-batch kernel's resident waves */
+    FKS_KERNEL_JOBS_SMALL_BATCH = 11, /* fks_simulate_<family>_jobs_small: a job batch whose particles
+                                         together fit the small-batch kernel's resident waves */
+    FKS_KERNEL_PATH_JOBS = 12,        /* fks_simulate_<family>[_lean]_path_jobs (fks_forward_simulate_path_jobs) */
+    FKS_KERNEL_PATH_JOBS_SMALL_BATCH = 13 /* fks_simulate_<family>_path_jobs_small: a path-job batch whose
+                                             particles together fit the small-batch kernel's resident waves */
 } fks_kernel_kind;
 /* The launch layout fks_set_robot chose (ABI 8; diagnostic, no reference counterpart). */
 typedef struct fks_launch_info {
@@ -790,6 +849,10 @@ fks_status fks_multi_forward_simulate_path(fks_multi_context* m, const double* s
  * every device consumes num_jobs call indices from the multi context's, which then advances by
  * num_jobs.  Refusals as fks_forward_simulate_jobs */
 fks_status fks_multi_forward_simulate_jobs(fks_multi_context* m, const fks_job* jobs, uint64_t num_jobs);
+/* fks_forward_simulate_path_jobs over the active devices, cut in the same way: of every job its
+ * shard meets a device gets the sub-range (its rows of every leg), and every other job empty
+ * with its num_legs kept, so all devices consume the same sum of num_legs call indices. */
+fks_status fks_multi_forward_simulate_path_jobs(fks_multi_context* m, const fks_path_job* jobs, uint64_t num_jobs);
 fks_status fks_multi_get_statistics(const fks_multi_context* m, fks_statistics* out);
 fks_status fks_multi_reset_statistics(fks_multi_context* m);
 fks_status fks_multi_get_last_call_counters(const fks_multi_context* m, fks_call_counters* out);
