@@ -222,7 +222,7 @@ class LaunchInfo(ctypes.Structure):
 
 KERNEL_KINDS = {0: "none", 1: "throughput", 2: "small_batch", 3: "shaped", 4: "traced", 5: "individual", 6: "cooperative",
                 7: "shaped_small_batch", 8: "path", 9: "path_small_batch", 10: "jobs", 11: "jobs_small_batch",
-                12: "path_jobs", 13: "path_jobs_small_batch"}
+                12: "path_jobs", 13: "path_jobs_small_batch", 14: "shaped_path_jobs", 15: "shaped_path_jobs_small_batch"}
 
 
 class Job(ctypes.Structure):
@@ -383,6 +383,9 @@ PROTOTYPES = [
     ("fks_set_specialization", c_int32, [c_void_p, c_int32]),
     ("fks_get_launch_info", c_int32, [c_void_p, POINTER(LaunchInfo)]),
     ("fks_get_specialization", c_int32, [c_void_p, POINTER(SpecializationInfo)]),
+    ("fks_prepare_batched_specialization", c_int32, [c_void_p]),
+    ("fks_set_batched_specialization", c_int32, [c_void_p, c_int32]),
+    ("fks_get_batched_specialization", c_int32, [c_void_p, POINTER(SpecializationInfo)]),
     ("fks_set_individual_jacobians", c_int32, [c_void_p, c_int32]),
     ("fks_env_build", c_int32, [POINTER(Obstacle), c_int32, c_double, POINTER(c_double), POINTER(c_int64), POINTER(c_void_p)]),
     ("fks_env_build_gpu", c_int32, [POINTER(Obstacle), c_int32, c_double, POINTER(c_double), POINTER(c_int64), c_int32,

@@ -197,5 +197,12 @@ def build_path_jobs_test(force: bool = False) -> str:
     return build_cpp_program(os.path.join("tests", "cpp", "path_jobs_interface_test.cpp"), "path_jobs_interface_test", force)
 
 
+def build_shaped_batches_test(force: bool = False) -> str:
+    """Compile tests/cpp/shaped_batches_interface_test.cpp: PrepareKernels(robot, batched=true) and
+    ForwardSimulateRobotsJobsAlongPaths on the batched shaped module against a second simulator
+    with specialisation off."""
+    return build_cpp_program(os.path.join("tests", "cpp", "shaped_batches_interface_test.cpp"), "shaped_batches_interface_test", force)
+
+
 if __name__ == "__main__":
     print(build_library(force=True, verbose=True))

@@ -395,6 +395,19 @@ struct fks_context {
     uint64_t spec_launches = 0;
     bool spec_failed = false;  /* the current robot's build failed (its calls run the generic kernel) */
     std::string spec_message;  /* why (fks_specialization_info.message) */
+    /* the batched module of the same shape (fks_set_batched_specialization): the kernels of
+     * path, job and path-job batches, built at the first batch that runs its throughput kernel */
+    int32_t bspec_enabled = 0; /* opt-in: fks_set_batched_specialization / fks_prepare_batched_specialization */
+    bool bspec_pending = false;
+    hipModule_t bspec_module = nullptr;
+    hipFunction_t bspec_fn = nullptr;       /* fks_simulate_shaped_pj */
+    hipFunction_t bspec_small_fn = nullptr; /* fks_simulate_shaped_pj_small (non-lean shapes) */
+    std::string bspec_shape;
+    double bspec_seconds = 0.0;
+    int32_t bspec_from_cache = 0;
+    uint64_t bspec_launches = 0;
+    bool bspec_failed = false;
+    std::string bspec_message;
 };
 
 template <typename T>
@@ -418,9 +431,12 @@ static fks_status hip_fail(fks_context* ctx, hipError_t e, const char* where) {
     } while (0)
 
 static void spec_release(fks_context* ctx);
+static void bspec_release(fks_context* ctx);
 
 static void free_robot(fks_context* ctx) {
     spec_release(ctx); /* a specialised kernel belongs to one robot shape */
+    bspec_release(ctx);
+    ctx->bspec_pending = false;
     for (void* p : ctx->robot_allocs) (void)hipFree(p);
     ctx->robot_allocs.clear();
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
@@ -464,6 +480,22 @@ static void spec_release(fks_context* ctx) {
     ctx->spec_message.clear();
 }
 
+static void bspec_release(fks_context* ctx) {
+    if (ctx->bspec_module) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipModuleUnload(ctx->bspec_module);
+    }
+    ctx->bspec_module = nullptr;
+    ctx->bspec_fn = nullptr;
+    ctx->bspec_small_fn = nullptr;
+    ctx->bspec_shape.clear();
+    ctx->bspec_seconds = 0.0;
+    ctx->bspec_from_cache = 0;
+    ctx->bspec_launches = 0;
+    ctx->bspec_failed = false;
+    ctx->bspec_message.clear();
+}
+
 static fks_status spec_build(fks_context* ctx);
 
 /* the shape-specialised throughput kernel of the current robot: compiled (or taken from a
@@ -484,7 +516,8 @@ static fks_status spec_prepare(fks_context* ctx) {
     return st;
 }
 
-static fks_status spec_build(fks_context* ctx) {
+/* what the specialised builds of the current robot fix at compile time */
+static fks_spec::Shape spec_shape_of(const fks_context* ctx) {
     fks_spec::Shape sh;
     sh.type = ctx->R.type;
     sh.L = ctx->R.L;
@@ -508,14 +541,17 @@ static fks_status spec_build(fks_context* ctx) {
         if (n == 0 || n == fksd::kThroughputWavesPerEU) sh.waves_per_eu = 0;
         else if (n >= per_simd && n <= 8) sh.waves_per_eu = n;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->spec_shape = fks_spec::shape_key(sh); /* named in the report even when the build fails */
+    return sh;
+}
+
+/* the code object of `sh` (a cache or a compile) loaded on the context's device */
+static fks_status spec_load(fks_context* ctx, const fks_spec::Shape& sh, std::shared_ptr<const fks_spec::CodeObject>* out_co,
+                            hipModule_t* out_m, bool* out_compiled) {
     std::string log;
     bool compiled = false;
     std::shared_ptr<const fks_spec::CodeObject> co = fks_spec::code_object(sh, &log, &compiled);
     if (!co) return fail(ctx, FKS_ERR_UNSUPPORTED, "shape specialisation: " + log);
     hipModule_t m = nullptr;
-    hipFunction_t f = nullptr;
     hipError_t e = hipModuleLoadData(&m, co->bytes.data());
     if (e != hipSuccess && !compiled) {
         /* a cached code object the runtime refuses (truncated, or from another toolchain):
@@ -526,21 +562,45 @@ static fks_status spec_build(fks_context* ctx) {
         e = hipModuleLoadData(&m, co->bytes.data());
     }
     if (e != hipSuccess) return hip_fail(ctx, e, "hipModuleLoadData (shape-specialised kernel)");
-    e = hipModuleGetFunction(&f, m, "fks_simulate_shaped");
+    *out_co = co;
+    *out_m = m;
+    *out_compiled = compiled;
+    return FKS_OK;
+}
+
+/* the throughput register budget of a shaped kernel: the persistent grid is sized for the
+ * generic kernel's occupancy, so a specialised kernel (same launch bounds, same LDS block) is
+ * used only if it needs no more registers.  512 VGPRs per SIMD lane, allocated in granules of 8 */
+static int spec_budget(const fks_context* ctx, const fks_spec::Shape& sh) {
+    hipFuncAttributes gen{};
+    if (hipFuncGetAttributes(&gen, reinterpret_cast<const void*>(kernel_for(ctx->R.type, false, ctx->lean))) != hipSuccess) gen.numRegs = 0;
+    return sh.waves_per_eu > 0 ? (512 / sh.waves_per_eu) & ~7 : gen.numRegs;
+}
+
+/* VGPRs plus AGPRs of kernel `name`, read from the code object's metadata (the runtime's
+ * attribute query reports a different quantity for module kernels than for the library's own) */
+static int spec_registers(const fks_spec::CodeObject& co, const char* name) {
+    return fks_spec::kernel_metadata_uint(co.bytes, name, ".vgpr_count") +
+           std::max(0, fks_spec::kernel_metadata_uint(co.bytes, name, ".agpr_count"));
+}
+
+static fks_status spec_build(fks_context* ctx) {
+    const fks_spec::Shape sh = spec_shape_of(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->spec_shape = fks_spec::shape_key(sh); /* named in the report even when the build fails */
+    std::shared_ptr<const fks_spec::CodeObject> co;
+    hipModule_t m = nullptr;
+    hipFunction_t f = nullptr;
+    bool compiled = false;
+    const fks_status ld = spec_load(ctx, sh, &co, &m, &compiled);
+    if (ld != FKS_OK) return ld;
+    const hipError_t e = hipModuleGetFunction(&f, m, "fks_simulate_shaped");
     if (e != hipSuccess) {
         (void)hipModuleUnload(m);
         return hip_fail(ctx, e, "hipModuleGetFunction(fks_simulate_shaped)");
     }
-    /* the persistent grid is sized for the generic kernel's occupancy: the specialised kernel
-     * (same launch bounds, same LDS block) is used only if it needs no more registers.  Its
-     * count is read from the code object's metadata (the runtime's attribute query reports a
-     * different quantity for module kernels than for the library's own) */
-    const int shaped_vgpr = fks_spec::kernel_metadata_uint(co->bytes, "fks_simulate_shaped", ".vgpr_count") +
-                            std::max(0, fks_spec::kernel_metadata_uint(co->bytes, "fks_simulate_shaped", ".agpr_count"));
-    hipFuncAttributes gen{};
-    if (hipFuncGetAttributes(&gen, reinterpret_cast<const void*>(kernel_for(ctx->R.type, false, ctx->lean))) != hipSuccess) gen.numRegs = 0;
-    /* 512 VGPRs per SIMD lane, allocated in granules of 8 */
-    const int budget = sh.waves_per_eu > 0 ? (512 / sh.waves_per_eu) & ~7 : gen.numRegs;
+    const int shaped_vgpr = spec_registers(*co, "fks_simulate_shaped");
+    const int budget = spec_budget(ctx, sh);
     if (shaped_vgpr <= 0 || shaped_vgpr > budget) {
         (void)hipModuleUnload(m);
         return fail(ctx, FKS_ERR_UNSUPPORTED,
@@ -556,8 +616,7 @@ static fks_status spec_build(fks_context* ctx) {
      * SIMD leave (the generic small-batch kernel's grid is the one launched) */
     hipFunction_t fs = nullptr;
     if (!ctx->lean && hipModuleGetFunction(&fs, m, "fks_simulate_shaped_small") == hipSuccess) {
-        const int v = fks_spec::kernel_metadata_uint(co->bytes, "fks_simulate_shaped_small", ".vgpr_count") +
-                      std::max(0, fks_spec::kernel_metadata_uint(co->bytes, "fks_simulate_shaped_small", ".agpr_count"));
+        const int v = spec_registers(*co, "fks_simulate_shaped_small");
         if (v > 0 && v <= 256) ctx->spec_small_fn = fs;
     }
     (void)hipGetLastError();
@@ -565,6 +624,72 @@ static fks_status spec_build(fks_context* ctx) {
     ctx->spec_seconds = compiled ? co->compile_seconds : 0.0;
     ctx->spec_from_cache = compiled ? 0 : 1;
     return FKS_OK;
+}
+
+/* the batched module of the current robot (Shape.batched: fks_simulate_shaped_pj[_small]), the
+ * plain module's rules applied to path, job and path-job batches: the same register gates, and
+ * a failure leaves the generic batched kernels in place and is recorded */
+static fks_status bspec_build(fks_context* ctx) {
+    fks_spec::Shape sh = spec_shape_of(ctx);
+    sh.batched = 1;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->bspec_shape = fks_spec::shape_key(sh);
+    std::shared_ptr<const fks_spec::CodeObject> co;
+    hipModule_t m = nullptr;
+    hipFunction_t f = nullptr;
+    bool compiled = false;
+    const fks_status ld = spec_load(ctx, sh, &co, &m, &compiled);
+    if (ld != FKS_OK) return ld;
+    const hipError_t e = hipModuleGetFunction(&f, m, "fks_simulate_shaped_pj");
+    if (e != hipSuccess) {
+        (void)hipModuleUnload(m);
+        return hip_fail(ctx, e, "hipModuleGetFunction(fks_simulate_shaped_pj)");
+    }
+    const int shaped_vgpr = spec_registers(*co, "fks_simulate_shaped_pj");
+    const int budget = spec_budget(ctx, sh);
+    if (shaped_vgpr <= 0 || shaped_vgpr > budget) {
+        (void)hipModuleUnload(m);
+        return fail(ctx, FKS_ERR_UNSUPPORTED,
+                    "shape specialisation: the specialised batch kernel needs " + std::to_string(shaped_vgpr) +
+                        " VGPRs, the budget is " + std::to_string(budget));
+    }
+    ctx->bspec_module = m;
+    ctx->bspec_fn = f;
+    hipFunction_t fs = nullptr;
+    if (!ctx->lean && hipModuleGetFunction(&fs, m, "fks_simulate_shaped_pj_small") == hipSuccess) {
+        const int v = spec_registers(*co, "fks_simulate_shaped_pj_small");
+        if (v > 0 && v <= 256) ctx->bspec_small_fn = fs;
+    }
+    (void)hipGetLastError();
+    ctx->bspec_seconds = compiled ? co->compile_seconds : 0.0;
+    ctx->bspec_from_cache = compiled ? 0 : 1;
+    return FKS_OK;
+}
+
+static fks_status bspec_prepare(fks_context* ctx) {
+    bspec_release(ctx);
+    if (ctx->specialize != FKS_SPECIALIZE_ON || !ctx->has_robot) return FKS_OK;
+    const fks_status st = bspec_build(ctx);
+    if (st != FKS_OK) {
+        ctx->bspec_failed = true;
+        ctx->bspec_message = ctx->last_error;
+        (void)hipGetLastError(); /* as spec_prepare */
+    }
+    return st;
+}
+
+/* whether a path, job or path-job batch runs the shaped batch kernels; builds the module at
+ * the first batch that would run its throughput kernel (a small batch never builds it), and
+ * a failed build adds to the last error without failing the call */
+static bool bspec_ready(fks_context* ctx, bool small) {
+    if (!ctx->bspec_enabled || ctx->specialize != FKS_SPECIALIZE_ON || ctx->individual_jacobians) return false;
+    if (ctx->bspec_pending && !small) {
+        ctx->bspec_pending = false;
+        const std::string keep = ctx->last_error;
+        if (bspec_prepare(ctx) != FKS_OK) ctx->last_error = keep + (keep.empty() ? "" : "; ") + ctx->last_error;
+        (void)hipSetDevice(ctx->device);
+    }
+    return small ? (ctx->bspec_fn && ctx->bspec_small_fn && !ctx->lean) : ctx->bspec_fn != nullptr;
 }
 
 extern "C" {
@@ -743,6 +868,7 @@ void fks_destroy(fks_context* ctx) {
     if (ctx->pending && ctx->pending_stream) (void)hipStreamSynchronize(ctx->pending_stream);
     (void)hipDeviceSynchronize();
     spec_release(ctx);
+    bspec_release(ctx);
     free_robot(ctx);
     free_staging(ctx);
     if (ctx->d_sdf) (void)hipFree(ctx->d_sdf);
@@ -1251,6 +1377,9 @@ fks_status fks_set_robot(fks_context* ctx, const fks_robot_desc* d) {
      * (simulate_device), so robots only ever simulated in small batches cost no compile */
     spec_release(ctx);
     ctx->spec_pending = ctx->specialize != 0;
+    /* ... and its batched module at the first path, job or path-job batch that runs it */
+    bspec_release(ctx);
+    ctx->bspec_pending = ctx->specialize == FKS_SPECIALIZE_ON;
     return FKS_OK;
 }
 
@@ -1324,6 +1453,19 @@ struct TraceDev {
     uint32_t step_cap, cfg_cap;
 };
 
+/* simulate_device's choice of the small-batch kernel for an untraced path, job or path-job batch
+ * of n particles (its `small`, from the same terms): whole particles (one segment) that fit
+ * the small-batch grid */
+static bool batch_is_small(const fks_context* ctx, uint64_t n) {
+    uint32_t nseg = 1;
+    if (n > 0 && (ctx->segment_steps != 0 || n > (uint64_t)ctx->grid_waves)) {
+        const uint32_t T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
+        const uint32_t k = std::min(ctx->segment_steps ? ctx->segment_steps : kDefaultSegmentSteps, T);
+        nseg = (uint32_t)(((uint64_t)T - 1u) / k + 1u);
+    }
+    return ctx->small_batch && !ctx->individual_jacobians && !ctx->lean && nseg == 1 && n <= (uint64_t)ctx->small_grid_waves;
+}
+
 static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint64_t n, const double* d_targets,
                                   uint64_t num_targets, uint64_t first_particle_id, int32_t allow_contacts,
                                   double* d_out_positions, uint8_t* d_out_collided, uint32_t* d_out_microsteps,
@@ -1362,6 +1504,46 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     fks_status st = settle(ctx);
     if (st != FKS_OK) return st;
+    if ((path || jobs) && n > 0 && path_legs <= FKS_MAX_PATH_JOB_LEGS && bspec_ready(ctx, batch_is_small(ctx, n))) {
+        /* the robot's batched module serves all three batched entries through its PATH && JOBS
+         * kernel: a path is one path job of path_legs legs, a job a path job of one leg.  The
+         * leg-major outputs, the keys (call indices) and the counters are the same either way */
+        std::vector<fks_path_job> as_pj(path ? 1 : (size_t)num_jobs);
+        for (size_t j = 0; j < as_pj.size(); ++j) {
+            fks_path_job& p = as_pj[j];
+            std::memset(&p, 0, sizeof(p));
+            if (path) {
+                p.starts = d_starts;
+                p.n = n;
+                p.waypoints = d_targets;
+                p.num_legs = path_legs;
+                p.num_targets = num_targets;
+                p.first_particle_id = first_particle_id;
+                p.allow_contacts = allow_contacts;
+                p.out_positions = d_out_positions;
+                p.out_collided = d_out_collided;
+                p.out_microsteps = d_out_microsteps;
+                p.out_resolver_iterations = d_out_resolver_iterations;
+                p.out_error_flags = d_out_error_flags;
+            } else {
+                const fks_job& job = jobs[j];
+                p.starts = job.starts;
+                p.n = job.n;
+                p.waypoints = job.targets;
+                p.num_legs = 1;
+                p.num_targets = job.num_targets;
+                p.first_particle_id = job.first_particle_id;
+                p.allow_contacts = job.allow_contacts;
+                p.out_positions = job.out_positions;
+                p.out_collided = job.out_collided;
+                p.out_microsteps = job.out_microsteps;
+                p.out_resolver_iterations = job.out_resolver_iterations;
+                p.out_error_flags = job.out_error_flags;
+            }
+        }
+        return simulate_device(ctx, nullptr, n, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, stream, synchronize, nullptr,
+                               nullptr, 0, nullptr, as_pj.size(), as_pj.data());
+    }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ctx->call_start = std::chrono::steady_clock::now();
     const uint64_t first_call = ctx->call_index;
@@ -1613,13 +1795,17 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
         if (spec_prepare(ctx) != FKS_OK) ctx->last_error = keep + (keep.empty() ? "" : "; ") + ctx->last_error;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
     }
-    /* (a path runs the generic path kernels: it neither builds nor launches the shape's module) */
+    /* a path-job batch runs the kernels of the robot's batched module (built here at the first
+     * batch past the small-batch grid, under the same rule; path and job batches arrive in
+     * path-job form when it serves them, see the entry above), the generic ones otherwise */
+    const bool shaped_pj = pjobs && bspec_ready(ctx, small);
     const bool shaped = ctx->spec_fn && !path && !jobs && !pjobs && !tr && !small && !coop && !ctx->individual_jacobians;
     /* a small batch runs the shape's small-batch kernel once the robot's module is built (it is
      * never built for a small batch: robots only ever simulated in small batches cost no compile) */
     const bool shaped_small = !path && !jobs && !pjobs && small && ctx->spec_fn && ctx->spec_small_fn;
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    ctx->last_kernel = pjobs ? (small ? FKS_KERNEL_PATH_JOBS_SMALL_BATCH : FKS_KERNEL_PATH_JOBS)
+    ctx->last_kernel = shaped_pj ? (small ? FKS_KERNEL_SHAPED_PATH_JOBS_SMALL_BATCH : FKS_KERNEL_SHAPED_PATH_JOBS)
+                       : pjobs ? (small ? FKS_KERNEL_PATH_JOBS_SMALL_BATCH : FKS_KERNEL_PATH_JOBS)
                        : jobs ? (small ? FKS_KERNEL_JOBS_SMALL_BATCH : FKS_KERNEL_JOBS)
                        : path ? (small ? FKS_KERNEL_PATH_SMALL_BATCH : FKS_KERNEL_PATH)
                        : tr ? FKS_KERNEL_TRACED
@@ -1628,7 +1814,13 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
                                     : (coop ? FKS_KERNEL_COOPERATIVE
                                             : (small ? FKS_KERNEL_SMALL_BATCH
                                                      : (ctx->individual_jacobians ? FKS_KERNEL_INDIVIDUAL : FKS_KERNEL_THROUGHPUT))));
-    if (shaped) {
+    if (shaped_pj) {
+        const fksd::SimArgs* argp = d_launch_args;
+        void* params[] = {&argp};
+        HIP_TRY(ctx, hipModuleLaunchKernel(small ? ctx->bspec_small_fn : ctx->bspec_fn, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1,
+                                           (unsigned)ctx->lds_bytes, s, params, nullptr));
+        ctx->bspec_launches++;
+    } else if (shaped) {
         const fksd::SimArgs* argp = ctx->d_args;
         void* params[] = {&argp};
         HIP_TRY(ctx, hipModuleLaunchKernel(ctx->spec_fn, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes, s,
@@ -2488,7 +2680,47 @@ fks_status fks_set_specialization(fks_context* ctx, int32_t mode) {
     if (st != FKS_OK) return st;
     ctx->specialize = mode;
     ctx->spec_pending = false;
+    /* the batched module is released with the plain one and, when the mode allows it, built
+     * again at the first batch that runs it (or by fks_prepare_batched_specialization): this
+     * call compiles the plain module only */
+    bspec_release(ctx);
+    ctx->bspec_pending = mode == FKS_SPECIALIZE_ON && ctx->has_robot;
     return spec_prepare(ctx); /* now, for the current robot (releases it when disabled) */
+}
+
+fks_status fks_prepare_batched_specialization(fks_context* ctx) {
+    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
+    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
+    if (ctx->specialize != FKS_SPECIALIZE_ON)
+        return fail(ctx, FKS_ERR_UNSUPPORTED, "the batched module needs fks_set_specialization(ctx, FKS_SPECIALIZE_ON)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const fks_status st = settle(ctx);
+    if (st != FKS_OK) return st;
+    ctx->bspec_enabled = 1;
+    ctx->bspec_pending = false;
+    if (ctx->bspec_fn) return FKS_OK; /* built already */
+    return bspec_prepare(ctx);
+}
+
+fks_status fks_set_batched_specialization(fks_context* ctx, int32_t enabled) {
+    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
+    ctx->bspec_enabled = enabled ? 1 : 0;
+    return FKS_OK;
+}
+
+fks_status fks_get_batched_specialization(const fks_context* ctx, fks_specialization_info* out) {
+    if (!ctx || !out) return FKS_ERR_INVALID_ARGUMENT;
+    std::memset(out, 0, sizeof(*out));
+    out->enabled = ctx->bspec_enabled;
+    out->active = ctx->bspec_fn ? 1 : 0;
+    out->pending = ctx->bspec_pending && ctx->bspec_enabled ? 1 : 0;
+    out->from_cache = ctx->bspec_from_cache;
+    out->compile_seconds = ctx->bspec_seconds;
+    out->launches = ctx->bspec_launches;
+    std::snprintf(out->shape, sizeof(out->shape), "%s", ctx->bspec_shape.c_str());
+    out->failed = ctx->bspec_failed ? 1 : 0;
+    std::snprintf(out->message, sizeof(out->message), "%s", ctx->bspec_message.c_str());
+    return FKS_OK;
 }
 
 fks_status fks_get_specialization(const fks_context* ctx, fks_specialization_info* out) {

@@ -4363,7 +4363,7 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
 #define FKS_WAVES_PER_EU 5 /* fksd::kThroughputWavesPerEU */
 #endif
 #define FKS_KERNEL_ATTRS __launch_bounds__(64 * kMaxWavesPerGroup) __attribute__((amdgpu_waves_per_eu(FKS_WAVES_PER_EU)))
-#if defined(FKS_SHAPE_L)
+#if defined(FKS_SHAPE_L) && !defined(FKS_SHAPE_BATCHED) /* (the batched flavour: at the end of the file) */
 /* the shape-specialised build (fks_specialize.cpp, hiprtc): one throughput kernel for one
  * robot shape, the same template and launch attributes as the generic kernel it replaces
  * (fks_simulate_<family>[_lean]); a robot whose LDS block keeps fewer waves resident than
@@ -4387,7 +4387,7 @@ fks_simulate_shaped_small(const SimArgs* __restrict__ args) {
     simulate_particles<FKS_SHAPE_TYPE, false>(args, lds_mem);
 }
 #endif
-#else
+#elif !defined(FKS_SHAPE_L)
 extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked(const SimArgs* __restrict__ args) {
     extern __shared__ __attribute__((aligned(16))) double lds_mem[];
     simulate_particles<FKS_ROBOT_LINKED, false>(args, lds_mem);
@@ -4619,4 +4619,26 @@ extern "C" __global__ void fks_math_probe(const double* a, const double* b, doub
     out[8 * i + 6] = fks_math::wrap_revolute(x / y); /* |x / y| from 1e-7 to beyond 1e9: the long division's every length */
     out[8 * i + 7] = (x * y + x) * y - x * x;
 }
+#endif
+
+#if defined(FKS_SHAPE_L) && defined(FKS_SHAPE_BATCHED)
+/* the batched flavour of the shape-specialised build (fks_specialize.cpp, Shape.batched): the
+ * PATH && JOBS instantiation of one robot shape, in a module of its own that holds nothing
+ * else.  It serves all three batched entries: a jobs call is a path-job batch whose jobs have
+ * one leg, a path call one with a single job (fks_capi.cpp turns both into path-job form).
+ * The names stay within 31 characters: fks_spec::kernel_metadata_uint matches a kernel's name
+ * as a MessagePack fixstr.  (Down here so that no other kernel's source line moves.) */
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_shaped_pj(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_SHAPE_TYPE, false, false, FKS_SHAPE_LEAN != 0, 0, true, true>(args, lds_mem);
+}
+#if !FKS_SHAPE_LEAN
+/* ... and at the small-batch budget (two waves per SIMD, as fks_simulate_shaped_small), for
+ * batches whose jobs together fit its resident waves once the module is built */
+extern "C" __global__ void __launch_bounds__(64 * kMaxWavesPerGroup) __attribute__((amdgpu_waves_per_eu(2)))
+fks_simulate_shaped_pj_small(const SimArgs* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_SHAPE_TYPE, false, false, false, 0, true, true>(args, lds_mem);
+}
+#endif
 #endif

@@ -33,10 +33,14 @@ struct Shape {
                                * per SIMD); fewer when the LDS block caps the resident waves lower,
                                * so the kernel may use the registers those absent waves leave */
     int32_t no_proofs = 0;    /* validation build: every skip proof compiled out (FKS_NO_SKIP_PROOFS) */
+    int32_t batched = 0;      /* the batched flavour (FKS_SHAPE_BATCHED): the module holds
+                               * fks_simulate_shaped_pj[_small], the kernels of path, job and
+                               * path-job batches, instead of the plain call's */
 };
 
 /* "t0-L8-J7-D7-W7-G8-P512-p1-l0" (+ "-w4" for a raised register budget, "-np" for the
- * validation build without skip proofs): names the shape in logs and cache files */
+ * validation build without skip proofs, "-b" for the batched flavour): names the shape in
+ * logs and cache files */
 std::string shape_key(const Shape& s);
 
 struct CodeObject {
@@ -57,9 +61,12 @@ std::shared_ptr<const CodeObject> code_object(const Shape& s, std::string* log, 
  * (MessagePack: the key string followed by a positive integer), e.g. ".vgpr_count"; -1 if
  * absent */
 int metadata_uint(const std::vector<char>& code_object, const char* key);
-/* the same field of the entry of kernel `name` (the module also carries the shaped
- * configuration check): the first `key` after the entry's ".name" (the keys of a kernel's
- * metadata map are emitted in sorted order, ".name" before ".sgpr_count" / ".vgpr_count") */
+/* the same field of the entry of kernel `name` (a module carries several kernels): the keys
+ * of a kernel's metadata map are emitted in sorted order, so a key sorted after ".name"
+ * (".sgpr_count", ".vgpr_count") is the first one behind the entry's name and one sorted
+ * before it (".agpr_count") the nearest one in front.  Neither search leaves the entry: it
+ * stops at the next or the previous kernel's ".name", and returns -1 when the entry lacks
+ * the key */
 int kernel_metadata_uint(const std::vector<char>& code_object, const char* name, const char* key);
 
 }  // namespace fks_spec

@@ -199,6 +199,28 @@ class HipParticleContactSimulator:
         _capi.check(self._lib.fks_get_specialization(self._ctx, ctypes.byref(info)), self._ctx, "specialization")
         return info.as_dict()
 
+    def prepare_batched_specialization(self):
+        """Build (or fetch from the caches) the current robot's batched module now: the shaped
+        kernels of path, job and path-job batches (fks_prepare_batched_specialization), and
+        switch those batches to it.  After set_batched_specialization(True) alone it is built at
+        the first such batch that outgrows the small-batch grid or runs in segments.  Raises
+        FksError with the compiler log when it cannot be built; the batches then keep the generic
+        kernels, with the same results."""
+        _capi.check(self._lib.fks_prepare_batched_specialization(self._ctx), self._ctx, "batched specialization")
+
+    def set_batched_specialization(self, enabled: bool = True):
+        """True runs path, job and path-job batches on the robot's batched shaped module
+        (fks_set_batched_specialization; off by default: the batches then run the generic
+        kernels while plain calls stay on the shaped one).  Results do not depend on it."""
+        _capi.check(self._lib.fks_set_batched_specialization(self._ctx, 1 if enabled else 0), self._ctx, "batched specialization")
+
+    def batched_specialization(self) -> dict:
+        """fks_get_batched_specialization: specialization()'s fields for the batched module (its
+        shape ends in "-b"; enabled is set_batched_specialization's value)."""
+        info = _capi.SpecializationInfo()
+        _capi.check(self._lib.fks_get_batched_specialization(self._ctx, ctypes.byref(info)), self._ctx, "batched specialization")
+        return info.as_dict()
+
     def set_individual_jacobians(self, simulate_with_individual_jacobians: bool):
         """The simulate_with_individual_jacobians constructor flag of the reference class
         (SPCS:420-423, 1629): True selects ComputeResolverCorrectionStepIndividualJacobians
@@ -703,6 +725,19 @@ class MultiDeviceSimulator:
         info = _capi.SpecializationInfo()
         ctx = self._lib.fks_multi_device_context(self._ctx, int(shard))
         _capi.check(self._lib.fks_get_specialization(ctx, ctypes.byref(info)), ctx, "specialization")
+        return info.as_dict()
+
+    def prepare_batched_specialization(self):
+        """fks_prepare_batched_specialization on every device's context (each decides for itself)."""
+        for shard in range(self.num_devices()):
+            ctx = self._lib.fks_multi_device_context(self._ctx, shard)
+            _capi.check(self._lib.fks_prepare_batched_specialization(ctx), ctx, "batched specialization")
+
+    def device_simulator_batched_specialization(self, shard: int = 0) -> dict:
+        """fks_get_batched_specialization of one device's context."""
+        info = _capi.SpecializationInfo()
+        ctx = self._lib.fks_multi_device_context(self._ctx, int(shard))
+        _capi.check(self._lib.fks_get_batched_specialization(ctx, ctypes.byref(info)), ctx, "batched specialization")
         return info.as_dict()
 
     def set_robot(self, robot: RobotDescription):

@@ -253,19 +253,31 @@ class DeviceSet {
      * time, where a planner expects setup cost) instead of inside the first large batch.  A
      * failed build is not an error: the calls keep the generic kernel and the returned status
      * says why.  mode: FKS_SPECIALIZE_OFF / _ON / _NO_PROOFS */
-    SpecializationStatus prepare_kernels(int32_t mode = FKS_SPECIALIZE_ON) const {
+    SpecializationStatus prepare_kernels(int32_t mode = FKS_SPECIALIZE_ON, bool batched = false) const {
         for_each([&](fks_context* c) {
             const fks_status st = fks_set_specialization(c, mode);
             if (st != FKS_OK && st != FKS_ERR_UNSUPPORTED) Check(st, c, "fks_set_specialization");
+            /* batched: also the module of path, job and path-job batches (mode _ON only; its
+             * record is batched_specialization_status) */
+            if (batched && mode == FKS_SPECIALIZE_ON) {
+                const fks_status sb = fks_prepare_batched_specialization(c);
+                if (sb != FKS_OK && sb != FKS_ERR_UNSUPPORTED) Check(sb, c, "fks_prepare_batched_specialization");
+            }
         });
         return specialization_status();
     }
-    SpecializationStatus specialization_status() const {
+    SpecializationStatus specialization_status() const { return status_of(false); }
+    /* the same record for the batched module (fks_get_batched_specialization) */
+    SpecializationStatus batched_specialization_status() const { return status_of(true); }
+    SpecializationStatus status_of(bool batched) const {
         SpecializationStatus s;
         s.active = true;
         for_each([&](fks_context* c) {
             fks_specialization_info i{};
-            Check(fks_get_specialization(c, &i), c, "fks_get_specialization");
+            if (batched)
+                Check(fks_get_batched_specialization(c, &i), c, "fks_get_batched_specialization");
+            else
+                Check(fks_get_specialization(c, &i), c, "fks_get_specialization");
             s.active = s.active && i.active != 0;
             s.pending = s.pending || i.pending != 0;
             if (i.failed && !s.failed) s.message = i.message;

@@ -574,12 +574,17 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
      * compile (2-20 s the first time on a machine, then from the disk cache) lands at setup and
      * not inside the first large ForwardSimulateRobots; SpecializationStatus reports whether the
      * calls run it, and the compiler log when its build failed (they then run the generic
-     * kernel).  Neither throws on a failed build. */
-    fks::SpecializationStatus PrepareKernels(const std::shared_ptr<BaseRobotType>& robot) {
+     * kernel).  Neither throws on a failed build.  batched = true also builds the module that
+     * ForwardSimulateRobotsAlongPath, ForwardSimulateRobotsJobs and
+     * ForwardSimulateRobotsJobsAlongPaths run (fks_prepare_batched_specialization; otherwise
+     * built inside the first such batch past the small-batch grid);
+     * BatchedSpecializationStatus is its record. */
+    fks::SpecializationStatus PrepareKernels(const std::shared_ptr<BaseRobotType>& robot, bool batched = false) {
         SetRobot(Derived(robot));
-        return dev_->prepare_kernels(FKS_SPECIALIZE_ON);
+        return dev_->prepare_kernels(FKS_SPECIALIZE_ON, batched);
     }
     fks::SpecializationStatus SpecializationStatus() const { return dev_->specialization_status(); }
+    fks::SpecializationStatus BatchedSpecializationStatus() const { return dev_->batched_specialization_status(); }
     /* the configuration capacity a traced call starts with (a longer trace is re-run once with
      * the exact size); RetriedTraces() counts those re-runs */
     void SetTraceCapacityHint(uint32_t configs) { trace_capacity_hint_ = configs > 0 ? configs : 1; }

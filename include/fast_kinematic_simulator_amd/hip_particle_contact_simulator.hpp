@@ -252,12 +252,14 @@ class HipParticleContactSimulator {
     bool LastBatchSharded() const { return dev_.last_sharded(); }
     int32_t LastBatchDevices() const { return dev_.last_devices(); }
     /* build `robot`'s shape-specialised kernel on every device now (see
-     * fast_kinematic_simulator.hpp PrepareKernels); never throws on a failed build */
-    fks::SpecializationStatus PrepareKernels(const RobotDescription& robot) {
+     * fast_kinematic_simulator.hpp PrepareKernels); never throws on a failed build.  batched:
+     * also the module of path, job and path-job batches (BatchedSpecializationStatus) */
+    fks::SpecializationStatus PrepareKernels(const RobotDescription& robot, bool batched = false) {
         SetRobot(robot);
-        return dev_.prepare_kernels(FKS_SPECIALIZE_ON);
+        return dev_.prepare_kernels(FKS_SPECIALIZE_ON, batched);
     }
     fks::SpecializationStatus SpecializationStatus() const { return dev_.specialization_status(); }
+    fks::SpecializationStatus BatchedSpecializationStatus() const { return dev_.batched_specialization_status(); }
 
     /* GetFrame (SPCS:517-520) */
     std::string GetFrame() const { return frame_; }

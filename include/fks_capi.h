@@ -339,8 +339,9 @@ fks_status fks_forward_simulate_device(fks_context* ctx, const double* d_starts,
  * consumes num_legs call indices.  A context with fks_set_individual_jacobians on returns
  * FKS_ERR_UNSUPPORTED.  fks_set_segment_steps / _policy / _heavy_relative and
  * fks_set_small_batch_kernel apply as to a plain call (fks_set_cooperative_waves does not);
- * the call runs the generic path kernels (FKS_KERNEL_PATH / FKS_KERNEL_PATH_SMALL_BATCH) and
- * never builds or launches the shape-specialised module. */
+ * the call runs the robot's batched shape-specialised module when that serves it
+ * (fks_prepare_batched_specialization: FKS_KERNEL_SHAPED_PATH_JOBS[_SMALL_BATCH]) and the
+ * generic path kernels (FKS_KERNEL_PATH / FKS_KERNEL_PATH_SMALL_BATCH) otherwise. */
 fks_status fks_forward_simulate_path(fks_context* ctx, const double* starts, uint64_t n, const double* waypoints,
                                      uint64_t num_legs, uint64_t num_targets, int32_t allow_contacts,
                                      double* out_positions, uint8_t* out_collided, uint32_t* out_microsteps,
@@ -395,8 +396,9 @@ typedef struct {
  * kernel (FKS_KERNEL_JOBS_SMALL_BATCH) when the sum fits small_batch_resident_waves, no
  * segments are set, the block is not lean and fks_set_small_batch_kernel is on; the throughput
  * jobs kernel (FKS_KERNEL_JOBS) otherwise.  fks_set_segment_steps / _policy / _heavy_relative
- * apply as to a plain call over the sum; fks_set_cooperative_waves does not apply, and the
- * call never builds or launches the shape-specialised module.
+ * apply as to a plain call over the sum; fks_set_cooperative_waves does not apply.  With the
+ * robot's batched shape-specialised module (fks_prepare_batched_specialization) the same choice
+ * runs its kernels instead (FKS_KERNEL_SHAPED_PATH_JOBS[_SMALL_BATCH]).
  * Host buffers: every job's inputs go up in one copy and each output array comes down in one. */
 fks_status fks_forward_simulate_jobs(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs);
 /* Same with the job array on the host and every pointer in it in HBM (see
@@ -450,8 +452,9 @@ typedef struct {
  * (FKS_KERNEL_PATH_JOBS_SMALL_BATCH) when the sum fits small_batch_resident_waves, no segments
  * are set, the block is not lean and fks_set_small_batch_kernel is on; the throughput kernel
  * (FKS_KERNEL_PATH_JOBS) otherwise.  fks_set_segment_steps / _policy / _heavy_relative apply as
- * to a plain call over the sum; fks_set_cooperative_waves does not apply, and the call never
- * builds or launches the shape-specialised module.
+ * to a plain call over the sum; fks_set_cooperative_waves does not apply.  With the robot's
+ * batched shape-specialised module (fks_prepare_batched_specialization) the same choice runs
+ * its kernels instead (FKS_KERNEL_SHAPED_PATH_JOBS[_SMALL_BATCH]).
  * Host buffers: every job's starts and waypoints go up in one copy and each output array comes
  * down in one. */
 fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs);
@@ -605,8 +608,12 @@ typedef enum {
     FKS_KERNEL_JOBS_SMALL_BATCH = 11, /* fks_simulate_<family>_jobs_small: a job batch whose particles
                                          together fit the small-batch kernel's resident waves */
     FKS_KERNEL_PATH_JOBS = 12,        /* fks_simulate_<family>[_lean]_path_jobs (fks_forward_simulate_path_jobs) */
-    FKS_KERNEL_PATH_JOBS_SMALL_BATCH = 13 /* fks_simulate_<family>_path_jobs_small: a path-job batch whose
-                                             particles together fit the small-batch kernel's resident waves */
+    FKS_KERNEL_PATH_JOBS_SMALL_BATCH = 13, /* fks_simulate_<family>_path_jobs_small: a path-job batch whose
+                                              particles together fit the small-batch kernel's resident waves */
+    FKS_KERNEL_SHAPED_PATH_JOBS = 14,      /* fks_simulate_shaped_pj of the robot's batched module: a path, job
+                                              or path-job batch (fks_prepare_batched_specialization) */
+    FKS_KERNEL_SHAPED_PATH_JOBS_SMALL_BATCH = 15 /* fks_simulate_shaped_pj_small: such a batch within the
+                                                    small-batch kernel's resident waves, once the module is built */
 } fks_kernel_kind;
 /* The launch layout fks_set_robot chose (ABI 8; diagnostic, no reference counterpart). */
 typedef struct fks_launch_info {
@@ -713,6 +720,31 @@ typedef struct fks_specialization_info {
     char message[512];       /* ABI 9: why it failed (the start of the compiler log), else empty */
 } fks_specialization_info;
 fks_status fks_get_specialization(const fks_context* ctx, fks_specialization_info* out);
+/* The batched module (added within ABI 10): the same robot shape's kernels for path, job and
+ * path-job batches (fks_forward_simulate_path / _jobs / _path_jobs and their _device forms), in
+ * a code object of its own whose shape key ends in "-b".  It is opt-in: a context keeps its
+ * batches on the generic kernels until fks_set_batched_specialization(ctx, 1) or
+ * fks_prepare_batched_specialization.  Once enabled, and with fks_set_specialization at
+ * FKS_SPECIALIZE_ON (OFF and NO_PROOFS keep batches on the generic kernels), it is built, or
+ * fetched from the caches above, at the first batch that runs its throughput kernel (more
+ * particles than small_batch_resident_waves, or segments set), or at once by
+ * fks_prepare_batched_specialization, which also enables it and returns FKS_ERR_UNSUPPORTED
+ * with the log when the build fails; fks_set_specialization itself builds only the plain
+ * module, and releases this one (built again at the next such batch).  A batch that fits
+ * the small-batch grid never builds it and runs the module's small-batch kernel only once the
+ * module exists (never on a lean block).  A failed build leaves the generic batched kernels in
+ * place (same results), sets failed / message here and adds to fks_get_last_error without
+ * failing the call.  All three entries then report FKS_KERNEL_SHAPED_PATH_JOBS[_SMALL_BATCH]:
+ * one PATH-and-JOBS kernel serves them (a path is one path job, a job a path job of one leg;
+ * a path of more than FKS_MAX_PATH_JOB_LEGS legs keeps the generic path kernel).  Results,
+ * statistics, counters and call indices are those of the generic kernels.
+ * fks_set_batched_specialization(ctx, 0), the default, keeps batches generic while plain calls
+ * stay shaped; a module already built is kept.  fks_get_batched_specialization fills the
+ * plain module's struct for this one (`enabled` is fks_set_batched_specialization's value,
+ * `pending` is set only while enabled). */
+fks_status fks_prepare_batched_specialization(fks_context* ctx);
+fks_status fks_set_batched_specialization(fks_context* ctx, int32_t enabled);
+fks_status fks_get_batched_specialization(const fks_context* ctx, fks_specialization_info* out);
 
 /* sums over every call since fks_create / fks_reset_total_counters */
 fks_status fks_get_total_counters(const fks_context* ctx, fks_call_counters* out);
