@@ -1,0 +1,114 @@
+/*
+ * fks_batch.h — the host-side plan of a batched call (fks_forward_simulate_path, _jobs and
+ * _path_jobs, on one context or sharded): one normal form for the three entries, their argument
+ * checks, the controller-step segment plan and the kernel-argument records.
+ *
+ * Nothing here calls the HIP runtime or reads an fks_context: the inputs come in a small struct,
+ * device pointers are only offset and stored, never dereferenced, so the unit is built and
+ * tested on a machine without a GPU (tests/cpp/batch_plan_test.cpp).
+ */
+#ifndef FKS_BATCH_H
+#define FKS_BATCH_H
+
+#include <hip/hip_vector_types.h> /* the vector types SimArgs names */
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "fks_capi.h"
+#include "fks_device.h"
+
+namespace fks_batch {
+
+/* controller steps per segment when a batch outnumbers the resident waves: short
+ * enough that a contact-heavy particle progresses from the start of the launch, long
+ * enough that the hand-over (resting state + one FK) costs < 1 % */
+constexpr uint32_t kDefaultSegmentSteps = 14; /* re-swept in round 6: profiles/r06p_sched_ab_cfg*.json */
+
+uint64_t splitmix64(uint64_t x);
+
+/* the refusal of a num_targets that is neither 1 nor n, as the plain calls word it too */
+constexpr const char* kTargetsOneOrN = "targets must be 1 or n (SPCS:792)";
+
+/* the kernels a batch runs: PATH reads one record per leg, JOBS one per job, PATH_JOBS one per
+ * (job, leg) through both prefix arrays (fks_device.h, SimArgs) */
+enum Form { PATH = 0, JOBS = 1, PATH_JOBS = 2 };
+
+/* the entry a batch came through: the row of its refusals' wording (fks_batch.cpp) */
+enum Entry { ENTRY_PATH_DEVICE = 0, ENTRY_PATH_HOST, ENTRY_JOBS, ENTRY_PATH_JOBS };
+
+/* what the plan reads of a context */
+struct Inputs {
+    uint64_t seed = 0, call_index = 0;
+    uint32_t T = 1;             /* controller steps of a call (forward_steps) */
+    uint32_t segment_steps = 0; /* fks_set_segment_steps (0: automatic) */
+    uint32_t grid_waves = 0, small_grid_waves = 0;
+    bool small_batch = true, individual_jacobians = false, lean = false;
+    uint32_t W = 0;          /* R.W: doubles per configuration */
+    uint32_t seg_stride = 0; /* doubles per particle in seg_state */
+    uint32_t heavy_per_step = 0, heavy_priority = 0, heavy_relative = 0; /* fks_set_segment_policy / _heavy_relative */
+    fksd::SimArgs base;      /* everything a record shares with a plain call's arguments */
+};
+
+/* controller-step segments of one launch over n particles of `legs` legs each */
+struct SegmentPlan {
+    bool segmented = false;
+    uint32_t seg_steps = 1, nseg = 1;
+    uint64_t refusal_nseg = 1; /* segments per leg as the 2^31 refusal counts them: the rule before "n > 0" */
+    bool small = false;        /* whole particles that fit the small-batch grid */
+    bool path_carry = false;   /* whole legs and a wave for every particle */
+    uint32_t seg_heavy_resolver = 0, seg_heavy_prio = 0, seg_heavy_rel = 0;
+    uint64_t seg_done_words = 0, seg_state_words = 0; /* what the launch needs of the two arrays (0: none) */
+};
+/* segmentable: false for a traced call, which runs whole */
+SegmentPlan plan_segments(const Inputs& in, uint64_t n, uint64_t legs, bool segmentable = true);
+/* seg_steps, nseg and the heavy-segment settings of a plan, into a call's arguments */
+void apply_segments(const SegmentPlan& p, fksd::SimArgs* a);
+
+/* The normal form: a span of path jobs.  A path is one path job, a job a path job of one leg. */
+struct Batch {
+    Form form = PATH_JOBS;
+    Entry entry = ENTRY_PATH_JOBS;
+    const fks_path_job* external = nullptr; /* the caller's path jobs ... */
+    std::vector<fks_path_job> converted;    /* ... or the normal form of a path or a job batch, or a staged copy */
+    uint64_t num_jobs = 0;                  /* as the caller passed it (refused before anything is read when too large) */
+    /* from check_arguments: the sum of n, of num_legs, the longest job's legs, the sum of n x num_legs */
+    uint64_t total = 0, legs = 0, max_legs = 0, rows = 0;
+    SegmentPlan plan; /* from plan_batch */
+
+    const fks_path_job* jobs() const { return converted.empty() ? external : converted.data(); }
+};
+void from_path(Batch* b, Entry entry, const double* starts, uint64_t n, const double* waypoints, uint64_t num_legs,
+               uint64_t num_targets, uint64_t first_particle_id, int32_t allow_contacts, double* out_positions,
+               uint8_t* out_collided, uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags);
+void from_jobs(Batch* b, const fks_job* jobs, uint64_t num_jobs);
+void from_path_jobs(Batch* b, const fks_path_job* jobs, uint64_t num_jobs);
+/* a one-leg path job as the job it came from */
+fks_job as_job(const fks_path_job& p);
+
+/* What an entry refuses before anything is staged or counted: FKS_OK, or the status with its
+ * text in *why.  Fills the batch's sums. */
+fks_status check_arguments(Batch* b, bool individual_jacobians, std::string* why);
+/* ... and what depends on the context's schedule: the segment plan and the 2^31 bound of a
+ * particle's ticket space.  check_arguments, then this. */
+fks_status plan_batch(const Inputs& in, Batch* b, std::string* why);
+
+/* the records of a planned batch */
+struct RecordPlan {
+    size_t records = 0;         /* SimArgs-sized units of the upload: the records, then job_first and leg_first */
+    uint64_t call_advance = 0;  /* what the call adds to the call index ... */
+    uint64_t particles = 0;     /* ... and to last.particles */
+    bool launch = false;        /* false: every job is empty, nothing is uploaded or launched */
+};
+RecordPlan plan_records(const Batch& b);
+/* Writes the upload into h_records (plan_records(b).records units): one record per (job, leg),
+ * job-major, then job_first[num_jobs + 1] and leg_first[num_jobs + 1].  d_records is where the
+ * upload will lie on the device, seg_state / seg_done the batch's arrays (null where the plan
+ * needs none). */
+void build_records(const Inputs& in, const Batch& b, double* seg_state, uint32_t* seg_done, const fksd::SimArgs* d_records,
+                   fksd::SimArgs* h_records);
+
+}  // namespace fks_batch
+
+#endif

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "fks_capi.h"
+#include "fks_batch.h"
 #include "fks_env_internal.h"
 #include "fks_specialize.h"
 #include "fks_device.h"
@@ -78,107 +79,38 @@ namespace {
 
 typedef void (*sim_kernel_t)(const fksd::SimArgs*);
 
-/* the batched CheckConfigCollision kernel for one robot family */
-sim_kernel_t check_kernel_for(int robot_type) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_check_configs_se2;
-        case FKS_ROBOT_SE3: return fks_check_configs_se3;
-        default: return fks_check_configs_linked;
-    }
+/* The library's kernels by form, register budget and robot family (FKS.cpp:4-71 factories).
+ * Forms: the plain simulation, its individual-Jacobian, traced and cooperative (one particle per
+ * workgroup) instantiations, the batched CheckConfigCollision, and the three batched forms in the
+ * order of fks_batch::Form.  Budget: throughput, or the low-occupancy instantiation for batches
+ * that fit its resident waves.  Family: a linked robot's lean LDS block (fks_set_robot) has
+ * kernels of its own where the throughput budget has them, the linked one's otherwise. */
+enum KernelForm { KF_PLAIN = 0, KF_INDIVIDUAL, KF_TRACED, KF_COOP, KF_CHECK, KF_PATH, KF_JOBS, KF_PATH_JOBS, KF_COUNT };
+static_assert(KF_JOBS == KF_PATH + fks_batch::JOBS && KF_PATH_JOBS == KF_PATH + fks_batch::PATH_JOBS, "batched forms in Form order");
+const sim_kernel_t kKernels[KF_COUNT][2][4] = {
+    /* linked, linked lean, SE(2), SE(3) */
+    {{fks_simulate_linked, fks_simulate_linked_lean, fks_simulate_se2, fks_simulate_se3},
+     {fks_simulate_linked_small, fks_simulate_linked_small, fks_simulate_se2_small, fks_simulate_se3_small}},
+    {{fks_simulate_linked_indiv, fks_simulate_linked_lean_indiv, fks_simulate_se2_indiv, fks_simulate_se3_indiv}, {}},
+    {{fks_simulate_linked_traced, fks_simulate_linked_lean_traced, fks_simulate_se2_traced, fks_simulate_se3_traced}, {}},
+    {{fks_simulate_linked_coop, fks_simulate_linked_coop, fks_simulate_se2_coop, fks_simulate_se3_coop}, {}},
+    {{fks_check_configs_linked, fks_check_configs_linked, fks_check_configs_se2, fks_check_configs_se3}, {}},
+    {{fks_simulate_linked_path, fks_simulate_linked_lean_path, fks_simulate_se2_path, fks_simulate_se3_path},
+     {fks_simulate_linked_path_small, fks_simulate_linked_path_small, fks_simulate_se2_path_small, fks_simulate_se3_path_small}},
+    {{fks_simulate_linked_jobs, fks_simulate_linked_lean_jobs, fks_simulate_se2_jobs, fks_simulate_se3_jobs},
+     {fks_simulate_linked_jobs_small, fks_simulate_linked_jobs_small, fks_simulate_se2_jobs_small, fks_simulate_se3_jobs_small}},
+    {{fks_simulate_linked_path_jobs, fks_simulate_linked_lean_path_jobs, fks_simulate_se2_path_jobs, fks_simulate_se3_path_jobs},
+     {fks_simulate_linked_path_jobs_small, fks_simulate_linked_path_jobs_small, fks_simulate_se2_path_jobs_small,
+      fks_simulate_se3_path_jobs_small}},
+};
+sim_kernel_t kernel_of(int form, bool small, int robot_type, bool lean = false) {
+    const int family = robot_type == FKS_ROBOT_SE2 ? 2 : (robot_type == FKS_ROBOT_SE3 ? 3 : (lean ? 1 : 0));
+    return kKernels[form][small ? 1 : 0][family];
 }
 
-/* the simulation kernel compiled for one robot family (FKS.cpp:4-71 factories) */
-/* lean: the robot runs a lean LDS block (linked robots only, fks_set_robot) */
-sim_kernel_t traced_kernel_for(int robot_type, bool lean = false) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_simulate_se2_traced;
-        case FKS_ROBOT_SE3: return fks_simulate_se3_traced;
-        default: return lean ? fks_simulate_linked_lean_traced : fks_simulate_linked_traced;
-    }
-}
-
-sim_kernel_t kernel_for(int robot_type, bool individual_jacobians = false, bool lean = false) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return individual_jacobians ? fks_simulate_se2_indiv : fks_simulate_se2;
-        case FKS_ROBOT_SE3: return individual_jacobians ? fks_simulate_se3_indiv : fks_simulate_se3;
-        default:
-            if (lean) return individual_jacobians ? fks_simulate_linked_lean_indiv : fks_simulate_linked_lean;
-            return individual_jacobians ? fks_simulate_linked_indiv : fks_simulate_linked;
-    }
-}
-
-/* the low-occupancy instantiation for batches that fit its resident waves */
-sim_kernel_t small_kernel_for(int robot_type) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_simulate_se2_small;
-        case FKS_ROBOT_SE3: return fks_simulate_se3_small;
-        default: return fks_simulate_linked_small;
-    }
-}
-
-/* the waypoint-path instantiations (fks_forward_simulate_path): throughput and small-batch budget */
-sim_kernel_t path_kernel_for(int robot_type, bool lean) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_simulate_se2_path;
-        case FKS_ROBOT_SE3: return fks_simulate_se3_path;
-        default: return lean ? fks_simulate_linked_lean_path : fks_simulate_linked_path;
-    }
-}
-sim_kernel_t path_small_kernel_for(int robot_type) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_simulate_se2_path_small;
-        case FKS_ROBOT_SE3: return fks_simulate_se3_path_small;
-        default: return fks_simulate_linked_path_small;
-    }
-}
-
-/* the job-batch instantiations (fks_forward_simulate_jobs): throughput and small-batch budget */
-sim_kernel_t jobs_kernel_for(int robot_type, bool lean) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_simulate_se2_jobs;
-        case FKS_ROBOT_SE3: return fks_simulate_se3_jobs;
-        default: return lean ? fks_simulate_linked_lean_jobs : fks_simulate_linked_jobs;
-    }
-}
-sim_kernel_t jobs_small_kernel_for(int robot_type) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_simulate_se2_jobs_small;
-        case FKS_ROBOT_SE3: return fks_simulate_se3_jobs_small;
-        default: return fks_simulate_linked_jobs_small;
-    }
-}
-
-/* the path-job instantiations (fks_forward_simulate_path_jobs): throughput and small-batch budget */
-sim_kernel_t path_jobs_kernel_for(int robot_type, bool lean) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_simulate_se2_path_jobs;
-        case FKS_ROBOT_SE3: return fks_simulate_se3_path_jobs;
-        default: return lean ? fks_simulate_linked_lean_path_jobs : fks_simulate_linked_path_jobs;
-    }
-}
-sim_kernel_t path_jobs_small_kernel_for(int robot_type) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_simulate_se2_path_jobs_small;
-        case FKS_ROBOT_SE3: return fks_simulate_se3_path_jobs_small;
-        default: return fks_simulate_linked_path_jobs_small;
-    }
-}
-
-/* the cooperative instantiation (one particle per workgroup) for batches of at most one
- * particle per resident workgroup */
-sim_kernel_t coop_kernel_for(int robot_type) {
-    switch (robot_type) {
-        case FKS_ROBOT_SE2: return fks_simulate_se2_coop;
-        case FKS_ROBOT_SE3: return fks_simulate_se3_coop;
-        default: return fks_simulate_linked_coop;
-    }
-}
+using fks_batch::splitmix64;
 
 using fksd::GridDev;
-/* controller steps per segment when a batch outnumbers the resident waves: short
- * enough that a contact-heavy particle progresses from the start of the launch, long
- * enough that the hand-over (resting state + one FK) costs < 1 % */
-constexpr uint32_t kDefaultSegmentSteps = 14; /* re-swept in round 6: profiles/r06p_sched_ab_cfg*.json */
 /* a segment averaging this many resolver iterations per controller step is
  * contact-heavy: its wave keeps the particle (the cfg3 batch averages 0.65) ... */
 constexpr uint32_t kHeavyResolverPerStep = 2;
@@ -210,12 +142,6 @@ GridDev make_grid(const fks_grid_geometry& g) {
     return d;
 }
 
-uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 uint32_t forward_steps(double time, double frequency) {
     const double raw = time * frequency;
@@ -300,6 +226,33 @@ static bool analyze_sdf(const float* v, int64_t nx, int64_t ny, int64_t nz, doub
     return *lplus > 0.0;
 }
 
+/* One robot shape's module of specialised kernels (fks_specialize.cpp), loaded on the context's
+ * device: the plain module (fks_set_specialization) and the batched one of the same shape
+ * (fks_set_batched_specialization) are two of these */
+struct ShapedModule {
+    hipModule_t module = nullptr;
+    hipFunction_t fn = nullptr;       /* the throughput kernel */
+    hipFunction_t small_fn = nullptr; /* the small-batch kernel (non-lean shapes) */
+    hipFunction_t check_fn = nullptr; /* fks_check_configs_shaped (the plain module only) */
+    std::string shape;
+    double seconds = 0.0;
+    int32_t from_cache = 0;
+    uint64_t launches = 0;
+    bool failed = false;  /* the current robot's build failed (its calls run the generic kernels) */
+    std::string message;  /* why (fks_specialization_info.message) */
+    bool pending = false; /* robot set, the module not built yet (built at the first launch that runs it) */
+};
+/* what tells the two modules apart */
+struct ShapedKind {
+    bool batched;         /* Shape.batched */
+    const char* fn;
+    const char* small_fn;
+    const char* check_fn; /* null: none */
+    const char* noun;     /* of the register refusal */
+};
+static const ShapedKind kPlainModule = {false, "fks_simulate_shaped", "fks_simulate_shaped_small", "fks_check_configs_shaped", "kernel"};
+static const ShapedKind kBatchedModule = {true, "fks_simulate_shaped_pj", "fks_simulate_shaped_pj_small", nullptr, "batch kernel"};
+
 struct fks_context {
     int device = 0;
     std::string last_error;
@@ -341,9 +294,9 @@ struct fks_context {
     unsigned long long* h_counters = nullptr; /* pinned */
     fksd::SimArgs* d_args = nullptr;          /* kernel arguments, read through a pointer */
     fksd::SimArgs* h_args = nullptr;          /* pinned staging for d_args */
-    fksd::SimArgs* d_path_args = nullptr;     /* a path call's records, one per leg (SimArgs.path_legs), or a job
-                                                 batch's, one per job (a path-job batch's, one per job and leg), then
-                                                 its job_first (SimArgs.job_first) */
+    fksd::SimArgs* d_path_args = nullptr;     /* a batch's records (fks_batch::build_records): one per (job, leg) of
+                                                 its normal form (a path's legs, a job batch's jobs), then job_first
+                                                 and leg_first (SimArgs.job_first) */
     fksd::SimArgs* h_path_args = nullptr;     /* pinned staging for d_path_args */
     size_t cap_path_args = 0;
     std::vector<unsigned char> jobs_stage;    /* fks_forward_simulate_jobs / _path_jobs: the jobs' inputs, then outputs, end to end */
@@ -384,30 +337,11 @@ struct fks_context {
     fks_call_counters total;
     /* robot-shape specialisation (fks_set_specialization, fks_specialize.cpp) */
     int32_t specialize = 1;
-    bool spec_pending = false; /* robot set, its kernel not built yet (built at the first launch that runs it) */
-    hipModule_t spec_module = nullptr;
-    hipFunction_t spec_fn = nullptr;       /* fks_simulate_shaped of the current robot's shape */
-    hipFunction_t spec_check_fn = nullptr; /* fks_check_configs_shaped (same module) */
-    hipFunction_t spec_small_fn = nullptr; /* fks_simulate_shaped_small (same module, non-lean shapes) */
-    std::string spec_shape;
-    double spec_seconds = 0.0;
-    int32_t spec_from_cache = 0;
-    uint64_t spec_launches = 0;
-    bool spec_failed = false;  /* the current robot's build failed (its calls run the generic kernel) */
-    std::string spec_message;  /* why (fks_specialization_info.message) */
+    ShapedModule spec; /* fks_simulate_shaped[_small] and fks_check_configs_shaped of the current robot's shape */
     /* the batched module of the same shape (fks_set_batched_specialization): the kernels of
      * path, job and path-job batches, built at the first batch that runs its throughput kernel */
     int32_t bspec_enabled = 0; /* opt-in: fks_set_batched_specialization / fks_prepare_batched_specialization */
-    bool bspec_pending = false;
-    hipModule_t bspec_module = nullptr;
-    hipFunction_t bspec_fn = nullptr;       /* fks_simulate_shaped_pj */
-    hipFunction_t bspec_small_fn = nullptr; /* fks_simulate_shaped_pj_small (non-lean shapes) */
-    std::string bspec_shape;
-    double bspec_seconds = 0.0;
-    int32_t bspec_from_cache = 0;
-    uint64_t bspec_launches = 0;
-    bool bspec_failed = false;
-    std::string bspec_message;
+    ShapedModule bspec;        /* fks_simulate_shaped_pj[_small] */
 };
 
 template <typename T>
@@ -430,13 +364,12 @@ static fks_status hip_fail(fks_context* ctx, hipError_t e, const char* where) {
         if (_e != hipSuccess) return hip_fail((ctx), _e, #expr); \
     } while (0)
 
-static void spec_release(fks_context* ctx);
-static void bspec_release(fks_context* ctx);
+static void shaped_release(fks_context* ctx, ShapedModule* m);
 
 static void free_robot(fks_context* ctx) {
-    spec_release(ctx); /* a specialised kernel belongs to one robot shape */
-    bspec_release(ctx);
-    ctx->bspec_pending = false;
+    shaped_release(ctx, &ctx->spec); /* a specialised kernel belongs to one robot shape */
+    shaped_release(ctx, &ctx->bspec);
+    ctx->bspec.pending = false;
     for (void* p : ctx->robot_allocs) (void)hipFree(p);
     ctx->robot_allocs.clear();
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
@@ -463,57 +396,15 @@ static void free_staging(fks_context* ctx) {
     ctx->cap_seg_state = ctx->cap_seg_done = 0;
 }
 
-static void spec_release(fks_context* ctx) {
-    if (ctx->spec_module) {
+/* unloads a module and clears its report; `pending` is the caller's to set */
+static void shaped_release(fks_context* ctx, ShapedModule* m) {
+    if (m->module) {
         (void)hipSetDevice(ctx->device);
-        (void)hipModuleUnload(ctx->spec_module);
+        (void)hipModuleUnload(m->module);
     }
-    ctx->spec_module = nullptr;
-    ctx->spec_fn = nullptr;
-    ctx->spec_check_fn = nullptr;
-    ctx->spec_small_fn = nullptr;
-    ctx->spec_shape.clear();
-    ctx->spec_seconds = 0.0;
-    ctx->spec_from_cache = 0;
-    ctx->spec_launches = 0;
-    ctx->spec_failed = false;
-    ctx->spec_message.clear();
-}
-
-static void bspec_release(fks_context* ctx) {
-    if (ctx->bspec_module) {
-        (void)hipSetDevice(ctx->device);
-        (void)hipModuleUnload(ctx->bspec_module);
-    }
-    ctx->bspec_module = nullptr;
-    ctx->bspec_fn = nullptr;
-    ctx->bspec_small_fn = nullptr;
-    ctx->bspec_shape.clear();
-    ctx->bspec_seconds = 0.0;
-    ctx->bspec_from_cache = 0;
-    ctx->bspec_launches = 0;
-    ctx->bspec_failed = false;
-    ctx->bspec_message.clear();
-}
-
-static fks_status spec_build(fks_context* ctx);
-
-/* the shape-specialised throughput kernel of the current robot: compiled (or taken from a
- * cache), loaded on the context's device, and used only if it keeps the generic kernel's
- * occupancy (the persistent grid is sized for that).  A failure leaves the generic kernel
- * in place and is recorded (fks_specialization_info.failed / message) */
-static fks_status spec_prepare(fks_context* ctx) {
-    spec_release(ctx);
-    if (!ctx->specialize || !ctx->has_robot) return FKS_OK;
-    const fks_status st = spec_build(ctx);
-    if (st != FKS_OK) {
-        ctx->spec_failed = true;
-        ctx->spec_message = ctx->last_error;
-        /* a failed module load can leave the runtime's per-thread error set; the generic
-         * launch that follows checks hipGetLastError and must not pick it up */
-        (void)hipGetLastError();
-    }
-    return st;
+    const bool pending = m->pending;
+    *m = ShapedModule();
+    m->pending = pending;
 }
 
 /* what the specialised builds of the current robot fix at compile time */
@@ -573,7 +464,7 @@ static fks_status spec_load(fks_context* ctx, const fks_spec::Shape& sh, std::sh
  * used only if it needs no more registers.  512 VGPRs per SIMD lane, allocated in granules of 8 */
 static int spec_budget(const fks_context* ctx, const fks_spec::Shape& sh) {
     hipFuncAttributes gen{};
-    if (hipFuncGetAttributes(&gen, reinterpret_cast<const void*>(kernel_for(ctx->R.type, false, ctx->lean))) != hipSuccess) gen.numRegs = 0;
+    if (hipFuncGetAttributes(&gen, reinterpret_cast<const void*>(kernel_of(KF_PLAIN, false, ctx->R.type, ctx->lean))) != hipSuccess) gen.numRegs = 0;
     return sh.waves_per_eu > 0 ? (512 / sh.waves_per_eu) & ~7 : gen.numRegs;
 }
 
@@ -584,112 +475,85 @@ static int spec_registers(const fks_spec::CodeObject& co, const char* name) {
            std::max(0, fks_spec::kernel_metadata_uint(co.bytes, name, ".agpr_count"));
 }
 
-static fks_status spec_build(fks_context* ctx) {
-    const fks_spec::Shape sh = spec_shape_of(ctx);
+/* A module of the current robot: compiled (or taken from a cache), loaded on the context's
+ * device, and used only if its throughput kernel keeps the generic kernel's occupancy (the
+ * persistent grid is sized for that).  The batched module (Shape.batched) applies the plain
+ * module's rules to path, job and path-job batches: the same register gates */
+static fks_status shaped_build(fks_context* ctx, ShapedModule* sm, const ShapedKind& kind) {
+    fks_spec::Shape sh = spec_shape_of(ctx);
+    sh.batched = kind.batched ? 1 : 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->spec_shape = fks_spec::shape_key(sh); /* named in the report even when the build fails */
+    sm->shape = fks_spec::shape_key(sh); /* named in the report even when the build fails */
     std::shared_ptr<const fks_spec::CodeObject> co;
     hipModule_t m = nullptr;
     hipFunction_t f = nullptr;
     bool compiled = false;
     const fks_status ld = spec_load(ctx, sh, &co, &m, &compiled);
     if (ld != FKS_OK) return ld;
-    const hipError_t e = hipModuleGetFunction(&f, m, "fks_simulate_shaped");
+    const hipError_t e = hipModuleGetFunction(&f, m, kind.fn);
     if (e != hipSuccess) {
         (void)hipModuleUnload(m);
-        return hip_fail(ctx, e, "hipModuleGetFunction(fks_simulate_shaped)");
+        return hip_fail(ctx, e, ("hipModuleGetFunction(" + std::string(kind.fn) + ")").c_str());
     }
-    const int shaped_vgpr = spec_registers(*co, "fks_simulate_shaped");
+    const int shaped_vgpr = spec_registers(*co, kind.fn);
     const int budget = spec_budget(ctx, sh);
     if (shaped_vgpr <= 0 || shaped_vgpr > budget) {
         (void)hipModuleUnload(m);
         return fail(ctx, FKS_ERR_UNSUPPORTED,
-                    "shape specialisation: the specialised kernel needs " + std::to_string(shaped_vgpr) + " VGPRs, the budget is " +
-                        std::to_string(budget));
+                    "shape specialisation: the specialised " + std::string(kind.noun) + " needs " + std::to_string(shaped_vgpr) +
+                        " VGPRs, the budget is " + std::to_string(budget));
     }
-    ctx->spec_module = m;
-    ctx->spec_fn = f;
+    sm->module = m;
+    sm->fn = f;
     /* the configuration check of the same shape, when the module carries it */
     hipFunction_t fc = nullptr;
-    if (hipModuleGetFunction(&fc, m, "fks_check_configs_shaped") == hipSuccess) ctx->spec_check_fn = fc;
+    if (kind.check_fn && hipModuleGetFunction(&fc, m, kind.check_fn) == hipSuccess) sm->check_fn = fc;
     /* ... and the small-batch kernel, used when it needs no more registers than two waves per
      * SIMD leave (the generic small-batch kernel's grid is the one launched) */
     hipFunction_t fs = nullptr;
-    if (!ctx->lean && hipModuleGetFunction(&fs, m, "fks_simulate_shaped_small") == hipSuccess) {
-        const int v = spec_registers(*co, "fks_simulate_shaped_small");
-        if (v > 0 && v <= 256) ctx->spec_small_fn = fs;
+    if (!ctx->lean && hipModuleGetFunction(&fs, m, kind.small_fn) == hipSuccess) {
+        const int v = spec_registers(*co, kind.small_fn);
+        if (v > 0 && v <= 256) sm->small_fn = fs;
     }
     (void)hipGetLastError();
-    ctx->spec_shape = fks_spec::shape_key(sh);
-    ctx->spec_seconds = compiled ? co->compile_seconds : 0.0;
-    ctx->spec_from_cache = compiled ? 0 : 1;
+    sm->seconds = compiled ? co->compile_seconds : 0.0;
+    sm->from_cache = compiled ? 0 : 1;
     return FKS_OK;
 }
 
-/* the batched module of the current robot (Shape.batched: fks_simulate_shaped_pj[_small]), the
- * plain module's rules applied to path, job and path-job batches: the same register gates, and
- * a failure leaves the generic batched kernels in place and is recorded */
-static fks_status bspec_build(fks_context* ctx) {
-    fks_spec::Shape sh = spec_shape_of(ctx);
-    sh.batched = 1;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->bspec_shape = fks_spec::shape_key(sh);
-    std::shared_ptr<const fks_spec::CodeObject> co;
-    hipModule_t m = nullptr;
-    hipFunction_t f = nullptr;
-    bool compiled = false;
-    const fks_status ld = spec_load(ctx, sh, &co, &m, &compiled);
-    if (ld != FKS_OK) return ld;
-    const hipError_t e = hipModuleGetFunction(&f, m, "fks_simulate_shaped_pj");
-    if (e != hipSuccess) {
-        (void)hipModuleUnload(m);
-        return hip_fail(ctx, e, "hipModuleGetFunction(fks_simulate_shaped_pj)");
-    }
-    const int shaped_vgpr = spec_registers(*co, "fks_simulate_shaped_pj");
-    const int budget = spec_budget(ctx, sh);
-    if (shaped_vgpr <= 0 || shaped_vgpr > budget) {
-        (void)hipModuleUnload(m);
-        return fail(ctx, FKS_ERR_UNSUPPORTED,
-                    "shape specialisation: the specialised batch kernel needs " + std::to_string(shaped_vgpr) +
-                        " VGPRs, the budget is " + std::to_string(budget));
-    }
-    ctx->bspec_module = m;
-    ctx->bspec_fn = f;
-    hipFunction_t fs = nullptr;
-    if (!ctx->lean && hipModuleGetFunction(&fs, m, "fks_simulate_shaped_pj_small") == hipSuccess) {
-        const int v = spec_registers(*co, "fks_simulate_shaped_pj_small");
-        if (v > 0 && v <= 256) ctx->bspec_small_fn = fs;
-    }
-    (void)hipGetLastError();
-    ctx->bspec_seconds = compiled ? co->compile_seconds : 0.0;
-    ctx->bspec_from_cache = compiled ? 0 : 1;
-    return FKS_OK;
-}
-
-static fks_status bspec_prepare(fks_context* ctx) {
-    bspec_release(ctx);
-    if (ctx->specialize != FKS_SPECIALIZE_ON || !ctx->has_robot) return FKS_OK;
-    const fks_status st = bspec_build(ctx);
+/* Releases the module and builds it for the current robot when the mode allows it: the plain
+ * module for any specialisation mode, the batched one only for FKS_SPECIALIZE_ON.  A failure
+ * leaves the generic kernels in place and is recorded (fks_specialization_info.failed / message) */
+static fks_status shaped_prepare(fks_context* ctx, ShapedModule* sm, const ShapedKind& kind) {
+    shaped_release(ctx, sm);
+    const bool allowed = kind.batched ? ctx->specialize == FKS_SPECIALIZE_ON : ctx->specialize != 0;
+    if (!allowed || !ctx->has_robot) return FKS_OK;
+    const fks_status st = shaped_build(ctx, sm, kind);
     if (st != FKS_OK) {
-        ctx->bspec_failed = true;
-        ctx->bspec_message = ctx->last_error;
-        (void)hipGetLastError(); /* as spec_prepare */
+        sm->failed = true;
+        sm->message = ctx->last_error;
+        /* a failed module load can leave the runtime's per-thread error set; the generic
+         * launch that follows checks hipGetLastError and must not pick it up */
+        (void)hipGetLastError();
     }
     return st;
 }
 
+/* the build at the first launch that runs a pending module: a failure keeps the generic kernels
+ * and adds to the last error (fks_get_specialization / fks_get_last_error) without failing the call */
+static void shaped_build_pending(fks_context* ctx, ShapedModule* sm, const ShapedKind& kind) {
+    sm->pending = false;
+    const std::string keep = ctx->last_error;
+    if (shaped_prepare(ctx, sm, kind) != FKS_OK) ctx->last_error = keep + (keep.empty() ? "" : "; ") + ctx->last_error;
+    (void)hipSetDevice(ctx->device);
+}
+
 /* whether a path, job or path-job batch runs the shaped batch kernels; builds the module at
- * the first batch that would run its throughput kernel (a small batch never builds it), and
- * a failed build adds to the last error without failing the call */
+ * the first batch that would run its throughput kernel (a small batch never builds it) */
 static bool bspec_ready(fks_context* ctx, bool small) {
     if (!ctx->bspec_enabled || ctx->specialize != FKS_SPECIALIZE_ON || ctx->individual_jacobians) return false;
-    if (ctx->bspec_pending && !small) {
-        ctx->bspec_pending = false;
-        const std::string keep = ctx->last_error;
-        if (bspec_prepare(ctx) != FKS_OK) ctx->last_error = keep + (keep.empty() ? "" : "; ") + ctx->last_error;
-        (void)hipSetDevice(ctx->device);
-    }
-    return small ? (ctx->bspec_fn && ctx->bspec_small_fn && !ctx->lean) : ctx->bspec_fn != nullptr;
+    if (ctx->bspec.pending && !small) shaped_build_pending(ctx, &ctx->bspec, kBatchedModule);
+    return small ? (ctx->bspec.fn && ctx->bspec.small_fn && !ctx->lean) : ctx->bspec.fn != nullptr;
 }
 
 extern "C" {
@@ -867,8 +731,8 @@ void fks_destroy(fks_context* ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->pending && ctx->pending_stream) (void)hipStreamSynchronize(ctx->pending_stream);
     (void)hipDeviceSynchronize();
-    spec_release(ctx);
-    bspec_release(ctx);
+    shaped_release(ctx, &ctx->spec);
+    shaped_release(ctx, &ctx->bspec);
     free_robot(ctx);
     free_staging(ctx);
     if (ctx->d_sdf) (void)hipFree(ctx->d_sdf);
@@ -913,8 +777,8 @@ static fks_status launch_layout(fks_context* ctx, const fksd::RobotDev& R) {
          * simulation, configuration check, kinematics) must hold that many groups: the
          * smallest occupancy of them all */
         const bool lean_l = l.lean != 0;
-        const sim_kernel_t kernels[] = {kernel_for(R.type, false, lean_l), kernel_for(R.type, true, lean_l),
-                                        traced_kernel_for(R.type, lean_l), check_kernel_for(R.type),
+        const sim_kernel_t kernels[] = {kernel_of(KF_PLAIN, false, R.type, lean_l), kernel_of(KF_INDIVIDUAL, false, R.type, lean_l),
+                                        kernel_of(KF_TRACED, false, R.type, lean_l), kernel_of(KF_CHECK, false, R.type),
                                         R.type == FKS_ROBOT_SE2 ? fks_kinematics_se2
                                                                 : (R.type == FKS_ROBOT_SE3 ? fks_kinematics_se3 : fks_kinematics_linked)};
         int n = 1 << 30;
@@ -992,7 +856,7 @@ static fks_status launch_layout(fks_context* ctx, const fksd::RobotDev& R) {
     ctx->small_grid_waves = 0;
     if (!lean) {
         int nk = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nk, reinterpret_cast<const void*>(small_kernel_for(R.type)), 64 * (int)wpg,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nk, reinterpret_cast<const void*>(kernel_of(KF_PLAIN, true, R.type)), 64 * (int)wpg,
                                                          bytes) == hipSuccess &&
             nk > 0)
             ctx->small_grid_waves = std::min<uint32_t>((uint32_t)(cus * nk) * wpg, ctx->grid_waves);
@@ -1008,9 +872,9 @@ static fks_status launch_layout(fks_context* ctx, const fksd::RobotDev& R) {
         const size_t cb = ((size_t)l.shared_total + l.total + fksd::kCoopBoxDoubles) * sizeof(double);
         hipFuncAttributes fa{};
         int nk = 0;
-        if (cb <= 160 * 1024 && hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(coop_kernel_for(R.type))) == hipSuccess &&
+        if (cb <= 160 * 1024 && hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel_of(KF_COOP, false, R.type))) == hipSuccess &&
             fa.maxThreadsPerBlock >= 128 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nk, reinterpret_cast<const void*>(coop_kernel_for(R.type)),
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nk, reinterpret_cast<const void*>(kernel_of(KF_COOP, false, R.type)),
                                                          fa.maxThreadsPerBlock, cb) == hipSuccess &&
             nk > 0) {
             ctx->coop_waves = (uint32_t)fa.maxThreadsPerBlock / 64u;
@@ -1375,11 +1239,11 @@ fks_status fks_set_robot(fks_context* ctx, const fks_robot_desc* d) {
     ctx->has_robot = true;
     /* the new robot's shape-specialised kernel is built at the first launch that runs it
      * (simulate_device), so robots only ever simulated in small batches cost no compile */
-    spec_release(ctx);
-    ctx->spec_pending = ctx->specialize != 0;
+    shaped_release(ctx, &ctx->spec);
+    ctx->spec.pending = ctx->specialize != 0;
     /* ... and its batched module at the first path, job or path-job batch that runs it */
-    bspec_release(ctx);
-    ctx->bspec_pending = ctx->specialize == FKS_SPECIALIZE_ON;
+    shaped_release(ctx, &ctx->bspec);
+    ctx->bspec.pending = ctx->specialize == FKS_SPECIALIZE_ON;
     return FKS_OK;
 }
 
@@ -1453,106 +1317,24 @@ struct TraceDev {
     uint32_t step_cap, cfg_cap;
 };
 
-/* simulate_device's choice of the small-batch kernel for an untraced path, job or path-job batch
- * of n particles (its `small`, from the same terms): whole particles (one segment) that fit
- * the small-batch grid */
-static bool batch_is_small(const fks_context* ctx, uint64_t n) {
-    uint32_t nseg = 1;
-    if (n > 0 && (ctx->segment_steps != 0 || n > (uint64_t)ctx->grid_waves)) {
-        const uint32_t T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
-        const uint32_t k = std::min(ctx->segment_steps ? ctx->segment_steps : kDefaultSegmentSteps, T);
-        nseg = (uint32_t)(((uint64_t)T - 1u) / k + 1u);
-    }
-    return ctx->small_batch && !ctx->individual_jacobians && !ctx->lean && nseg == 1 && n <= (uint64_t)ctx->small_grid_waves;
-}
-
-static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint64_t n, const double* d_targets,
-                                  uint64_t num_targets, uint64_t first_particle_id, int32_t allow_contacts,
-                                  double* d_out_positions, uint8_t* d_out_collided, uint32_t* d_out_microsteps,
-                                  uint32_t* d_out_resolver_iterations, uint32_t* d_out_error_flags, void* stream,
-                                  int32_t synchronize, const TraceDev* tr, double* d_pid_io = nullptr, uint64_t path_legs = 0,
-                                  const fks_job* jobs = nullptr, uint64_t num_jobs = 0, const fks_path_job* pjobs = nullptr) {
-    /* path_legs > 0: fks_forward_simulate_path (d_targets holds the waypoints, the outputs are
-     * leg-major); jobs: fks_forward_simulate_jobs (n is the jobs' sum, the particle arguments are
-     * each job's own, already checked by jobs_arguments); pjobs: fks_forward_simulate_path_jobs
-     * (as jobs, checked by path_jobs_arguments; every job has its own legs); none: a plain call */
-    const bool path = path_legs > 0;
-    uint64_t pj_legs = 0, pj_max_legs = 0, pj_rows = 0; /* a path-job batch's legs, longest job and sum of n x legs */
-    for (uint64_t j = 0; pjobs && j < num_jobs; ++j) {
-        pj_legs += pjobs[j].num_legs;
-        pj_max_legs = std::max<uint64_t>(pj_max_legs, pjobs[j].num_legs);
-        pj_rows += pjobs[j].n * pjobs[j].num_legs;
-    }
-    /* legs of a particle's ticket space (seg_done counts legs x nseg segments) */
-    const uint64_t space_legs = path ? path_legs : (pjobs ? pj_max_legs : 1u);
-    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
-    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
-    if (!jobs && !pjobs && n > 0 && (!d_starts || !d_targets || !d_out_positions))
-        return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "null device buffer");
-    if (n > 0 && num_targets != 1 && num_targets != n)
-        return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "targets must be 1 or n (SPCS:792)");
-    if (n > 0xffffffffull) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per call");
-    if (path || pjobs) {
-        /* seg_done counts a particle's segments over all legs in 31 bits (the top bit marks a claim) */
-        const uint32_t T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
-        const uint32_t k = std::min(ctx->segment_steps ? ctx->segment_steps : kDefaultSegmentSteps, T);
-        const bool segmented = ctx->segment_steps != 0 || n > (uint64_t)ctx->grid_waves; /* as below */
-        const uint64_t nseg = segmented ? ((uint64_t)T - 1u) / k + 1u : 1u;
-        if (space_legs >= (1ull << 31) || space_legs * nseg >= (1ull << 31))
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "legs x segments per leg must stay below 2^31");
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    fks_status st = settle(ctx);
-    if (st != FKS_OK) return st;
-    if ((path || jobs) && n > 0 && path_legs <= FKS_MAX_PATH_JOB_LEGS && bspec_ready(ctx, batch_is_small(ctx, n))) {
-        /* the robot's batched module serves all three batched entries through its PATH && JOBS
-         * kernel: a path is one path job of path_legs legs, a job a path job of one leg.  The
-         * leg-major outputs, the keys (call indices) and the counters are the same either way */
-        std::vector<fks_path_job> as_pj(path ? 1 : (size_t)num_jobs);
-        for (size_t j = 0; j < as_pj.size(); ++j) {
-            fks_path_job& p = as_pj[j];
-            std::memset(&p, 0, sizeof(p));
-            if (path) {
-                p.starts = d_starts;
-                p.n = n;
-                p.waypoints = d_targets;
-                p.num_legs = path_legs;
-                p.num_targets = num_targets;
-                p.first_particle_id = first_particle_id;
-                p.allow_contacts = allow_contacts;
-                p.out_positions = d_out_positions;
-                p.out_collided = d_out_collided;
-                p.out_microsteps = d_out_microsteps;
-                p.out_resolver_iterations = d_out_resolver_iterations;
-                p.out_error_flags = d_out_error_flags;
-            } else {
-                const fks_job& job = jobs[j];
-                p.starts = job.starts;
-                p.n = job.n;
-                p.waypoints = job.targets;
-                p.num_legs = 1;
-                p.num_targets = job.num_targets;
-                p.first_particle_id = job.first_particle_id;
-                p.allow_contacts = job.allow_contacts;
-                p.out_positions = job.out_positions;
-                p.out_collided = job.out_collided;
-                p.out_microsteps = job.out_microsteps;
-                p.out_resolver_iterations = job.out_resolver_iterations;
-                p.out_error_flags = job.out_error_flags;
-            }
-        }
-        return simulate_device(ctx, nullptr, n, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, stream, synchronize, nullptr,
-                               nullptr, 0, nullptr, as_pj.size(), as_pj.data());
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    ctx->call_start = std::chrono::steady_clock::now();
-    const uint64_t first_call = ctx->call_index;
-    const uint64_t key = splitmix64(ctx->seed ^ splitmix64(first_call));
-    ctx->call_index += path ? path_legs : (jobs ? num_jobs : (pjobs ? pj_legs : 1u));
-    std::memset(&ctx->last, 0, sizeof(ctx->last));
-    ctx->last.particles = path ? n * path_legs : (pjobs ? pj_rows : n); /* a path's counters are its chain's sums */
-    if ((path || jobs || pjobs) && n == 0) return FKS_OK; /* the chain's calls would launch nothing either */
-    fksd::SimArgs a;
+/* what the plan of a launch (fks_batch.h) reads of the context: its schedule settings and the
+ * arguments every call on it shares */
+static void plan_inputs(const fks_context* ctx, fks_batch::Inputs* in) {
+    in->seed = ctx->seed;
+    in->call_index = ctx->call_index;
+    in->T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
+    in->segment_steps = ctx->segment_steps;
+    in->grid_waves = ctx->grid_waves;
+    in->small_grid_waves = ctx->small_grid_waves;
+    in->small_batch = ctx->small_batch != 0;
+    in->individual_jacobians = ctx->individual_jacobians != 0;
+    in->lean = ctx->lean;
+    in->W = (uint32_t)ctx->R.W;
+    in->seg_stride = 2u * (uint32_t)ctx->R.D + 4u + (uint32_t)fksd::kRoundState * (uint32_t)std::min(ctx->R.nrounds, 64);
+    in->heavy_per_step = ctx->heavy_per_step;
+    in->heavy_priority = ctx->heavy_priority;
+    in->heavy_relative = ctx->heavy_relative;
+    fksd::SimArgs& a = in->base;
     std::memset(&a, 0, sizeof(a));
     a.sdf_g = ctx->sdf_g;
     a.nrm_g = ctx->nrm_g;
@@ -1572,22 +1354,8 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     a.target_micro = ctx->env_g.res * 0.125;
     a.allowed_micro = ctx->env_g.res * 1.0;
     a.time_multiplier = 1.0 / a.dt;
-    a.T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
-    a.key0 = (uint32_t)key;
-    a.key1 = (uint32_t)(key >> 32);
-    a.starts = d_starts;
-    a.targets = d_targets;
-    a.num_targets = num_targets;
-    a.n = n;
-    a.first_pid = first_particle_id;
-    a.allow_contacts = allow_contacts ? 1 : 0;
+    a.T = in->T;
     a.individual_jacobians = ctx->individual_jacobians;
-    a.out_q = d_out_positions;
-    a.pid_io = d_pid_io;
-    a.out_collided = d_out_collided;
-    a.out_micro = d_out_microsteps;
-    a.out_resolver = d_out_resolver_iterations;
-    a.out_err = d_out_error_flags;
     a.counters = ctx->d_counters;
     a.queue = ctx->d_counters + fksd::kNumCounters;
     a.scratch = ctx->d_scratch;
@@ -1595,259 +1363,211 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     a.row_cap = 3u * (uint32_t)ctx->R.P;
     a.L = fksd::make_lds_layout(ctx->R.L, ctx->R.J, ctx->R.D, ctx->R.W, ctx->R.G, ctx->R.nrounds, ctx->fk_pair, ctx->lean);
     a.SL = fksd::make_scratch_layout(a.row_cap, ctx->R.D, ctx->R.P, ctx->R.G);
-    /* controller-step segments: automatically only when the batch outnumbers the
-     * resident waves (otherwise every particle has a wave from the start), always
-     * when set explicitly (fks_set_segment_steps); traced calls run whole */
-    a.seg_steps = a.T;
-    a.nseg = 1;
-    a.seg_stride = 2u * (uint32_t)ctx->R.D + 4u + (uint32_t)fksd::kRoundState * (uint32_t)std::min(ctx->R.nrounds, 64);
-    if (!tr && n > 0 && (ctx->segment_steps != 0 || n > (uint64_t)ctx->grid_waves)) {
-        uint32_t k = ctx->segment_steps ? ctx->segment_steps : kDefaultSegmentSteps;
-        if (k > a.T) k = a.T;
-        a.seg_steps = k;
-        /* T >= 1 and k >= 1: ceil(T / k) without the uint32 wrap of (T + k - 1) / k */
-        a.nseg = (uint32_t)(((uint64_t)a.T - 1u) / k + 1u);
-        /* heavy_per_step <= 65536 (fks_set_segment_policy): the product fits in 64 bits,
-         * and the kernel compares it with a per-segment count of at most 2^32 - 1 */
-        const uint64_t heavy = (uint64_t)ctx->heavy_per_step * k;
-        a.seg_heavy_resolver = (uint32_t)std::min<uint64_t>(heavy, 0xffffffffull);
-        a.seg_heavy_prio = ctx->heavy_priority;
-        /* the relative test's running sums pack 24 bits of segments: off for larger batches */
-        a.seg_heavy_rel = ((uint64_t)n * a.nseg * space_legs < (1ull << 24)) ? ctx->heavy_relative : 0u;
-    }
-    /* a path's segment space is path_legs x nseg, so seg_done is needed from two legs on */
-    const uint64_t segments = (uint64_t)a.nseg * space_legs;
-    if (segments > 1 && a.nseg == 1) {
-        if (n > ctx->cap_seg_done) {
-            HIP_TRY(ctx, ensure(&ctx->d_seg_done, (size_t)n));
-            ctx->cap_seg_done = (size_t)n;
+    a.seg_stride = in->seg_stride;
+}
+
+/* One launch of a simulation kernel: a plain call (device buffers; optionally traced, or over
+ * the particles' own controller state), or a batch that its entry has checked and planned. */
+struct SimRequest {
+    fks_job plain{};                           /* a plain call's arguments ... */
+    const TraceDev* trace = nullptr;           /* fks_forward_simulate_traced */
+    double* d_pid_io = nullptr;                /* fks_forward_simulate_mutable */
+    const fks_batch::Batch* batch = nullptr;   /* ... or a batch in its normal form, */
+    const fks_batch::Inputs* inputs = nullptr; /* with the inputs it was planned from */
+    void* stream = nullptr;
+    int32_t synchronize = 1;
+};
+
+static fks_job plain_call(const double* d_starts, uint64_t n, const double* d_targets, uint64_t num_targets, uint64_t first_particle_id,
+                          int32_t allow_contacts, double* d_out_positions, uint8_t* d_out_collided, uint32_t* d_out_microsteps,
+                          uint32_t* d_out_resolver_iterations, uint32_t* d_out_error_flags) {
+    fks_job c{};
+    c.starts = d_starts;
+    c.n = n;
+    c.targets = d_targets;
+    c.num_targets = num_targets;
+    c.first_particle_id = first_particle_id;
+    c.allow_contacts = allow_contacts;
+    c.out_positions = d_out_positions;
+    c.out_collided = d_out_collided;
+    c.out_microsteps = d_out_microsteps;
+    c.out_resolver_iterations = d_out_resolver_iterations;
+    c.out_error_flags = d_out_error_flags;
+    return c;
+}
+
+/* what a request launches: one of the library's kernels, or one of a shaped module's */
+struct Launch {
+    int32_t kind = FKS_KERNEL_NONE; /* fks_get_launch_info: last_kernel */
+    sim_kernel_t kernel = nullptr;
+    hipFunction_t shaped = nullptr;
+    ShapedModule* module = nullptr; /* of `shaped`: its launches are counted */
+    bool coop = false;              /* the cooperative geometry: one workgroup per particle */
+};
+
+/* The kernel of a request over n particles under `plan`.  A pending shaped module is built
+ * here, at the first launch that would run its throughput kernel (never for a small batch:
+ * robots only ever simulated in small batches cost no compile). */
+static Launch choose_kernel(fks_context* ctx, const SimRequest& rq, const fks_batch::SegmentPlan& plan, uint64_t n) {
+    Launch l;
+    const int rt = ctx->R.type;
+    if (rq.batch) {
+        /* the robot's batched module serves all three forms through its PATH && JOBS kernel when
+         * the records fit its bound; otherwise the generic kernel of the batch's own form */
+        const fks_batch::Batch& b = *rq.batch;
+        static const int32_t kGeneric[3][2] = {{FKS_KERNEL_PATH, FKS_KERNEL_PATH_SMALL_BATCH},
+                                               {FKS_KERNEL_JOBS, FKS_KERNEL_JOBS_SMALL_BATCH},
+                                               {FKS_KERNEL_PATH_JOBS, FKS_KERNEL_PATH_JOBS_SMALL_BATCH}};
+        if (b.legs <= FKS_MAX_PATH_JOB_LEGS && bspec_ready(ctx, plan.small)) {
+            l.kind = plan.small ? FKS_KERNEL_SHAPED_PATH_JOBS_SMALL_BATCH : FKS_KERNEL_SHAPED_PATH_JOBS;
+            l.shaped = plan.small ? ctx->bspec.small_fn : ctx->bspec.fn;
+            l.module = &ctx->bspec;
+        } else {
+            l.kind = kGeneric[b.form][plan.small ? 1 : 0];
+            l.kernel = kernel_of(KF_PATH + b.form, plan.small, rt, ctx->lean);
         }
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_seg_done, 0, (size_t)n * sizeof(uint32_t), s));
-        a.seg_done = ctx->d_seg_done;
+        return l;
     }
-    if (a.nseg > 1) {
-        const size_t words = (size_t)n * a.seg_stride;
-        if (words > ctx->cap_seg_state) {
-            HIP_TRY(ctx, ensure(&ctx->d_seg_state, words));
-            ctx->cap_seg_state = words;
+    const bool individual = ctx->individual_jacobians != 0;
+    if (rq.trace) {
+        l.kind = FKS_KERNEL_TRACED;
+        l.kernel = kernel_of(KF_TRACED, false, rt, ctx->lean);
+    } else if (ctx->small_batch && ctx->cooperative && !individual && !ctx->lean && plan.nseg == 1 && n > 0 &&
+               n <= (uint64_t)ctx->coop_particles) {
+        l.kind = FKS_KERNEL_COOPERATIVE;
+        l.kernel = kernel_of(KF_COOP, false, rt);
+        l.coop = true;
+    } else if (plan.small) {
+        /* the shape's small-batch kernel once the robot's module is built */
+        const bool shaped = ctx->spec.fn && ctx->spec.small_fn;
+        l.kind = shaped ? FKS_KERNEL_SHAPED_SMALL_BATCH : FKS_KERNEL_SMALL_BATCH;
+        l.shaped = shaped ? ctx->spec.small_fn : nullptr;
+        l.module = shaped ? &ctx->spec : nullptr;
+        l.kernel = kernel_of(KF_PLAIN, true, rt);
+    } else if (individual) {
+        l.kind = FKS_KERNEL_INDIVIDUAL;
+        l.kernel = kernel_of(KF_INDIVIDUAL, false, rt, ctx->lean);
+    } else {
+        /* the plain throughput path runs the robot's shape-specialised kernel */
+        if (ctx->spec.pending) shaped_build_pending(ctx, &ctx->spec, kPlainModule);
+        l.kind = ctx->spec.fn ? FKS_KERNEL_SHAPED : FKS_KERNEL_THROUGHPUT;
+        l.shaped = ctx->spec.fn;
+        l.module = ctx->spec.fn ? &ctx->spec : nullptr;
+        l.kernel = kernel_of(KF_PLAIN, false, rt, ctx->lean);
+    }
+    return l;
+}
+
+static fks_status simulate_device(fks_context* ctx, const SimRequest& rq) {
+    const fks_batch::Batch* batch = rq.batch; /* checked by its entry (fks_batch::check_arguments, plan_batch) */
+    const fks_job& call = rq.plain;
+    const TraceDev* tr = rq.trace;
+    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
+    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
+    if (!batch) {
+        if (call.n > 0 && (!call.starts || !call.targets || !call.out_positions))
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "null device buffer");
+        if (call.n > 0 && call.num_targets != 1 && call.num_targets != call.n)
+            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, fks_batch::kTargetsOneOrN);
+        if (call.n > 0xffffffffull) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per call");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    fks_status st = settle(ctx);
+    if (st != FKS_OK) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(rq.stream);
+    ctx->call_start = std::chrono::steady_clock::now();
+    fks_batch::Inputs plain_inputs;
+    if (!batch) plan_inputs(ctx, &plain_inputs);
+    const fks_batch::Inputs& in = batch ? *rq.inputs : plain_inputs;
+    const uint64_t n = batch ? batch->total : call.n;
+    fks_batch::RecordPlan records;
+    if (batch) records = fks_batch::plan_records(*batch);
+    ctx->call_index += batch ? records.call_advance : 1u;
+    std::memset(&ctx->last, 0, sizeof(ctx->last));
+    ctx->last.particles = batch ? records.particles : n;
+    if (batch && !records.launch) return FKS_OK;
+    const fks_batch::SegmentPlan plan = batch ? batch->plan : fks_batch::plan_segments(in, n, 1, /*segmentable=*/!tr);
+    double* seg_state = nullptr;
+    uint32_t* seg_done = nullptr;
+    if (plan.seg_state_words) {
+        if (plan.seg_state_words > ctx->cap_seg_state) {
+            HIP_TRY(ctx, ensure(&ctx->d_seg_state, (size_t)plan.seg_state_words));
+            ctx->cap_seg_state = (size_t)plan.seg_state_words;
         }
-        if (n > ctx->cap_seg_done) {
-            HIP_TRY(ctx, ensure(&ctx->d_seg_done, (size_t)n));
-            ctx->cap_seg_done = (size_t)n;
+        seg_state = ctx->d_seg_state;
+    }
+    if (plan.seg_done_words) {
+        if (plan.seg_done_words > ctx->cap_seg_done) {
+            HIP_TRY(ctx, ensure(&ctx->d_seg_done, (size_t)plan.seg_done_words));
+            ctx->cap_seg_done = (size_t)plan.seg_done_words;
         }
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_seg_done, 0, (size_t)n * sizeof(uint32_t), s));
-        a.seg_state = ctx->d_seg_state;
-        a.seg_done = ctx->d_seg_done;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_seg_done, 0, (size_t)plan.seg_done_words * sizeof(uint32_t), s));
+        seg_done = ctx->d_seg_done;
     }
-    if (tr) {
-        a.tr_inputs = tr->inputs;
-        a.tr_micro = tr->micro;
-        a.tr_cfg = tr->cfg;
-        a.tr_tags = tr->tags;
-        a.tr_nsteps = tr->nsteps;
-        a.tr_ncfg = tr->ncfg;
-        a.tr_step_cap = tr->step_cap;
-        a.tr_cfg_cap = tr->cfg_cap;
-    }
-    /* a batch that fits the small-batch kernel's resident waves, whole particles, plain
-     * simulation: that kernel (every particle has its wave from the start either way) */
-    const bool coop = !path && !jobs && !pjobs && ctx->small_batch && ctx->cooperative && !tr && !ctx->individual_jacobians && !ctx->lean &&
-                      a.nseg == 1 && n > 0 && n <= (uint64_t)ctx->coop_particles;
-    const bool small = !coop && ctx->small_batch && !tr && !ctx->individual_jacobians && !ctx->lean && a.nseg == 1 &&
-                       n <= (uint64_t)ctx->small_grid_waves;
     const fksd::SimArgs* d_launch_args = ctx->d_args;
-    /* a job batch's records are followed by its job_first[num_jobs + 1], in whole records */
-    const size_t first_records = jobs ? ((size_t)(num_jobs + 1) * sizeof(uint32_t) + sizeof(fksd::SimArgs) - 1) / sizeof(fksd::SimArgs) : 0;
-    /* ... and a path-job batch's, one per (job, leg), by job_first and leg_first[num_jobs + 1] */
-    const size_t pj_first_records = pjobs ? (2 * (size_t)(num_jobs + 1) * sizeof(uint32_t) + sizeof(fksd::SimArgs) - 1) / sizeof(fksd::SimArgs) : 0;
-    const size_t records = path ? (size_t)path_legs : (pjobs ? (size_t)pj_legs + pj_first_records : (size_t)num_jobs + first_records);
-    /* the previous call has settled, so the pinned staging copies are free */
-    if ((path || jobs || pjobs) && records > ctx->cap_path_args) {
-        if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
-        ctx->h_path_args = nullptr;
-        ctx->cap_path_args = 0;
-        HIP_TRY(ctx, ensure(&ctx->d_path_args, records));
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_path_args, records * sizeof(fksd::SimArgs), 0));
-        ctx->cap_path_args = records;
-    }
-    if (pjobs) {
-        /* job-major, one record per (job, leg): a job's records are its path's (below) with the
-         * job's own arguments, the key of the sequence's call index, and the job's slices of the
-         * segment arrays; the two prefix arrays follow the records in the same upload */
-        const uint64_t W = (uint64_t)ctx->R.W;
-        uint32_t* h_first = reinterpret_cast<uint32_t*>(ctx->h_path_args + pj_legs);
-        uint32_t* h_leg_first = h_first + num_jobs + 1;
-        a.job_first = reinterpret_cast<const uint32_t*>(ctx->d_path_args + pj_legs);
-        a.num_jobs = (uint32_t)num_jobs;
-        a.jobs_total = n;
-        a.path_legs_max = (uint32_t)pj_max_legs;
-        /* whole legs and a wave for every particle: the wave keeps its particle through its job's legs */
-        a.path_carry = (a.nseg == 1 && n <= (uint64_t)(small ? ctx->small_grid_waves : ctx->grid_waves)) ? 1u : 0u;
-        uint64_t base = 0, rec = 0;
-        for (uint64_t j = 0; j < num_jobs; ++j) {
-            const fks_path_job& job = pjobs[j];
-            h_first[j] = (uint32_t)base;
-            h_leg_first[j] = (uint32_t)rec;
-            for (uint64_t leg = 0; leg < job.num_legs; ++leg) {
-                fksd::SimArgs& r = ctx->h_path_args[rec + leg];
-                r = a;
-                const uint64_t leg_key = splitmix64(ctx->seed ^ splitmix64(first_call + rec + leg));
-                r.key0 = (uint32_t)leg_key;
-                r.key1 = (uint32_t)(leg_key >> 32);
-                r.path_legs = (uint32_t)job.num_legs;
-                r.num_targets = job.num_targets;
-                r.n = job.n;
-                r.first_pid = job.first_particle_id;
-                r.allow_contacts = job.allow_contacts ? 1 : 0;
-                r.seg_state = a.seg_state ? a.seg_state + base * a.seg_stride : nullptr;
-                r.seg_done = a.seg_done ? a.seg_done + base : nullptr;
-                r.job_base = (uint32_t)base;
-                if (job.n == 0) continue; /* never read: no particle maps to an empty job */
-                r.targets = job.waypoints + leg * job.num_targets * W;
-                r.starts = leg == 0 ? job.starts : job.out_positions + (leg - 1) * job.n * W;
-                r.out_q = job.out_positions + leg * job.n * W;
-                r.out_collided = job.out_collided ? job.out_collided + leg * job.n : nullptr;
-                r.out_micro = job.out_microsteps ? job.out_microsteps + leg * job.n : nullptr;
-                r.out_resolver = job.out_resolver_iterations ? job.out_resolver_iterations + leg * job.n : nullptr;
-                r.out_err = job.out_error_flags ? job.out_error_flags + leg * job.n : nullptr;
-            }
-            base += job.n;
-            rec += job.num_legs;
+    if (batch) {
+        /* the previous call has settled, so the pinned staging copies are free */
+        if (records.records > ctx->cap_path_args) {
+            if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
+            ctx->h_path_args = nullptr;
+            ctx->cap_path_args = 0;
+            HIP_TRY(ctx, ensure(&ctx->d_path_args, records.records));
+            HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_path_args, records.records * sizeof(fksd::SimArgs), 0));
+            ctx->cap_path_args = records.records;
         }
-        h_first[num_jobs] = (uint32_t)base; /* == n */
-        h_leg_first[num_jobs] = (uint32_t)rec;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path_args, ctx->h_path_args, records * sizeof(fksd::SimArgs), hipMemcpyHostToDevice, s));
-        d_launch_args = ctx->d_path_args;
-    } else if (jobs) {
-        /* one record per job: the same call over all n particles except for the job's key (the
-         * sequence's call index), its own arguments and outputs, and its slices of the segment
-         * arrays, which start at the job's first global particle */
-        uint32_t* h_first = reinterpret_cast<uint32_t*>(ctx->h_path_args + num_jobs);
-        a.job_first = reinterpret_cast<const uint32_t*>(ctx->d_path_args + num_jobs);
-        a.num_jobs = (uint32_t)num_jobs;
-        a.jobs_total = n;
-        uint64_t base = 0;
-        for (uint64_t j = 0; j < num_jobs; ++j) {
-            const fks_job& job = jobs[j];
-            fksd::SimArgs& r = ctx->h_path_args[j];
-            r = a;
-            const uint64_t job_key = splitmix64(ctx->seed ^ splitmix64(first_call + j));
-            r.key0 = (uint32_t)job_key;
-            r.key1 = (uint32_t)(job_key >> 32);
-            r.starts = job.starts;
-            r.targets = job.targets;
-            r.num_targets = job.num_targets;
-            r.n = job.n;
-            r.first_pid = job.first_particle_id;
-            r.allow_contacts = job.allow_contacts ? 1 : 0;
-            r.out_q = job.out_positions;
-            r.out_collided = job.out_collided;
-            r.out_micro = job.out_microsteps;
-            r.out_resolver = job.out_resolver_iterations;
-            r.out_err = job.out_error_flags;
-            r.seg_state = a.seg_state ? a.seg_state + base * a.seg_stride : nullptr;
-            r.seg_done = a.seg_done ? a.seg_done + base : nullptr;
-            r.job_base = (uint32_t)base;
-            h_first[j] = (uint32_t)base;
-            base += job.n;
-        }
-        h_first[num_jobs] = (uint32_t)base; /* == n */
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path_args, ctx->h_path_args, records * sizeof(fksd::SimArgs), hipMemcpyHostToDevice, s));
-        d_launch_args = ctx->d_path_args;
-    } else if (path) {
-        /* one record per leg: the same call except for the leg's key (the chain's call index),
-         * waypoints, start configurations (the leg before's output slice) and output slices */
-        const uint64_t W = (uint64_t)ctx->R.W;
-        a.path_legs = (uint32_t)path_legs;
-        /* whole legs and a wave for every particle: the wave keeps its particle through all legs */
-        a.path_carry = (a.nseg == 1 && n <= (uint64_t)(small ? ctx->small_grid_waves : ctx->grid_waves)) ? 1u : 0u;
-        for (uint64_t leg = 0; leg < path_legs; ++leg) {
-            fksd::SimArgs& r = ctx->h_path_args[leg];
-            r = a;
-            const uint64_t leg_key = splitmix64(ctx->seed ^ splitmix64(first_call + leg));
-            r.key0 = (uint32_t)leg_key;
-            r.key1 = (uint32_t)(leg_key >> 32);
-            r.targets = d_targets + leg * num_targets * W;
-            r.starts = leg == 0 ? d_starts : d_out_positions + (leg - 1) * n * W;
-            r.out_q = d_out_positions + leg * n * W;
-            r.out_collided = d_out_collided ? d_out_collided + leg * n : nullptr;
-            r.out_micro = d_out_microsteps ? d_out_microsteps + leg * n : nullptr;
-            r.out_resolver = d_out_resolver_iterations ? d_out_resolver_iterations + leg * n : nullptr;
-            r.out_err = d_out_error_flags ? d_out_error_flags + leg * n : nullptr;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path_args, ctx->h_path_args, (size_t)path_legs * sizeof(fksd::SimArgs),
-                                    hipMemcpyHostToDevice, s));
+        fks_batch::build_records(in, *batch, seg_state, seg_done, ctx->d_path_args, ctx->h_path_args);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path_args, ctx->h_path_args, records.records * sizeof(fksd::SimArgs), hipMemcpyHostToDevice, s));
         d_launch_args = ctx->d_path_args;
     } else {
-        *ctx->h_args = a;
+        fksd::SimArgs& a = *ctx->h_args;
+        a = in.base;
+        const uint64_t key = splitmix64(in.seed ^ splitmix64(in.call_index));
+        a.key0 = (uint32_t)key;
+        a.key1 = (uint32_t)(key >> 32);
+        a.starts = call.starts;
+        a.targets = call.targets;
+        a.num_targets = call.num_targets;
+        a.n = n;
+        a.first_pid = call.first_particle_id;
+        a.allow_contacts = call.allow_contacts ? 1 : 0;
+        a.out_q = call.out_positions;
+        a.pid_io = rq.d_pid_io;
+        a.out_collided = call.out_collided;
+        a.out_micro = call.out_microsteps;
+        a.out_resolver = call.out_resolver_iterations;
+        a.out_err = call.out_error_flags;
+        fks_batch::apply_segments(plan, &a);
+        a.seg_state = seg_state;
+        a.seg_done = seg_done;
+        if (tr) {
+            a.tr_inputs = tr->inputs;
+            a.tr_micro = tr->micro;
+            a.tr_cfg = tr->cfg;
+            a.tr_tags = tr->tags;
+            a.tr_nsteps = tr->nsteps;
+            a.tr_ncfg = tr->ncfg;
+            a.tr_step_cap = tr->step_cap;
+            a.tr_cfg_cap = tr->cfg_cap;
+        }
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_args, ctx->h_args, sizeof(a), hipMemcpyHostToDevice, s));
     }
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, fksd::kCounterWords * sizeof(unsigned long long), s));
     const uint64_t groups_needed = (n + ctx->waves_per_group - 1) / ctx->waves_per_group;
     const uint32_t grid = (uint32_t)((groups_needed < (uint64_t)ctx->grid_groups) ? (groups_needed > 0 ? groups_needed : 1)
                                                                                   : ctx->grid_groups);
-    /* the plain throughput path runs the robot's shape-specialised kernel: built (or fetched
-     * from a cache) here at the first such launch; a failure keeps the generic kernel and is
-     * reported by fks_get_specialization / fks_get_last_error, not by this call */
-    if (ctx->spec_pending && !path && !jobs && !pjobs && !tr && !small && !coop && !ctx->individual_jacobians) {
-        ctx->spec_pending = false;
-        const std::string keep = ctx->last_error;
-        if (spec_prepare(ctx) != FKS_OK) ctx->last_error = keep + (keep.empty() ? "" : "; ") + ctx->last_error;
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-    }
-    /* a path-job batch runs the kernels of the robot's batched module (built here at the first
-     * batch past the small-batch grid, under the same rule; path and job batches arrive in
-     * path-job form when it serves them, see the entry above), the generic ones otherwise */
-    const bool shaped_pj = pjobs && bspec_ready(ctx, small);
-    const bool shaped = ctx->spec_fn && !path && !jobs && !pjobs && !tr && !small && !coop && !ctx->individual_jacobians;
-    /* a small batch runs the shape's small-batch kernel once the robot's module is built (it is
-     * never built for a small batch: robots only ever simulated in small batches cost no compile) */
-    const bool shaped_small = !path && !jobs && !pjobs && small && ctx->spec_fn && ctx->spec_small_fn;
+    const Launch l = choose_kernel(ctx, rq, plan, n);
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    ctx->last_kernel = shaped_pj ? (small ? FKS_KERNEL_SHAPED_PATH_JOBS_SMALL_BATCH : FKS_KERNEL_SHAPED_PATH_JOBS)
-                       : pjobs ? (small ? FKS_KERNEL_PATH_JOBS_SMALL_BATCH : FKS_KERNEL_PATH_JOBS)
-                       : jobs ? (small ? FKS_KERNEL_JOBS_SMALL_BATCH : FKS_KERNEL_JOBS)
-                       : path ? (small ? FKS_KERNEL_PATH_SMALL_BATCH : FKS_KERNEL_PATH)
-                       : tr ? FKS_KERNEL_TRACED
-                          : (shaped ? FKS_KERNEL_SHAPED
-                                    : shaped_small ? FKS_KERNEL_SHAPED_SMALL_BATCH
-                                    : (coop ? FKS_KERNEL_COOPERATIVE
-                                            : (small ? FKS_KERNEL_SMALL_BATCH
-                                                     : (ctx->individual_jacobians ? FKS_KERNEL_INDIVIDUAL : FKS_KERNEL_THROUGHPUT))));
-    if (shaped_pj) {
+    ctx->last_kernel = l.kind;
+    if (l.shaped) {
         const fksd::SimArgs* argp = d_launch_args;
         void* params[] = {&argp};
-        HIP_TRY(ctx, hipModuleLaunchKernel(small ? ctx->bspec_small_fn : ctx->bspec_fn, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1,
-                                           (unsigned)ctx->lds_bytes, s, params, nullptr));
-        ctx->bspec_launches++;
-    } else if (shaped) {
-        const fksd::SimArgs* argp = ctx->d_args;
-        void* params[] = {&argp};
-        HIP_TRY(ctx, hipModuleLaunchKernel(ctx->spec_fn, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes, s,
-                                           params, nullptr));
-        ctx->spec_launches++;
-    } else if (shaped_small) {
-        const fksd::SimArgs* argp = ctx->d_args;
-        void* params[] = {&argp};
-        HIP_TRY(ctx, hipModuleLaunchKernel(ctx->spec_small_fn, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes,
-                                           s, params, nullptr));
-        ctx->spec_launches++;
-    } else if (coop) {
-        hipLaunchKernelGGL(coop_kernel_for(ctx->R.type), dim3((uint32_t)n), dim3(64 * ctx->coop_waves), ctx->coop_lds_bytes, s,
-                           static_cast<const fksd::SimArgs*>(ctx->d_args));
-    } else if (pjobs) {
-        hipLaunchKernelGGL(small ? path_jobs_small_kernel_for(ctx->R.type) : path_jobs_kernel_for(ctx->R.type, ctx->lean), dim3(grid),
-                           dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
-    } else if (jobs) {
-        hipLaunchKernelGGL(small ? jobs_small_kernel_for(ctx->R.type) : jobs_kernel_for(ctx->R.type, ctx->lean), dim3(grid),
-                           dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
-    } else if (path) {
-        hipLaunchKernelGGL(small ? path_small_kernel_for(ctx->R.type) : path_kernel_for(ctx->R.type, ctx->lean), dim3(grid),
-                           dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
+        HIP_TRY(ctx, hipModuleLaunchKernel(l.shaped, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes, s, params,
+                                           nullptr));
+        l.module->launches++;
+    } else if (l.coop) {
+        hipLaunchKernelGGL(l.kernel, dim3((uint32_t)n), dim3(64 * ctx->coop_waves), ctx->coop_lds_bytes, s, d_launch_args);
     } else {
-        hipLaunchKernelGGL(tr ? traced_kernel_for(ctx->R.type, ctx->lean)
-                              : (small ? small_kernel_for(ctx->R.type) : kernel_for(ctx->R.type, ctx->individual_jacobians != 0, ctx->lean)),
-                           dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, static_cast<const fksd::SimArgs*>(ctx->d_args));
+        hipLaunchKernelGGL(l.kernel, dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
@@ -1856,7 +1576,7 @@ static fks_status simulate_device(fks_context* ctx, const double* d_starts, uint
     ctx->pending = true;
     ctx->pending_kind = 0;
     ctx->pending_stream = s;
-    if (synchronize) return settle(ctx);
+    if (rq.synchronize) return settle(ctx);
     return FKS_OK;
 }
 
@@ -1867,9 +1587,12 @@ fks_status fks_forward_simulate_device(fks_context* ctx, const double* d_starts,
                                        double* d_out_positions, uint8_t* d_out_collided, uint32_t* d_out_microsteps,
                                        uint32_t* d_out_resolver_iterations, uint32_t* d_out_error_flags, void* stream,
                                        int32_t synchronize) {
-    return simulate_device(ctx, d_starts, n, d_targets, num_targets, first_particle_id, allow_contacts, d_out_positions,
-                           d_out_collided, d_out_microsteps, d_out_resolver_iterations, d_out_error_flags, stream,
-                           synchronize, nullptr);
+    SimRequest rq;
+    rq.plain = plain_call(d_starts, n, d_targets, num_targets, first_particle_id, allow_contacts, d_out_positions, d_out_collided,
+                          d_out_microsteps, d_out_resolver_iterations, d_out_error_flags);
+    rq.stream = stream;
+    rq.synchronize = synchronize;
+    return simulate_device(ctx, rq);
 }
 
 fks_status fks_check_config_collision_device(fks_context* ctx, const double* d_configs, uint64_t n, double inflation_ratio,
@@ -1920,21 +1643,16 @@ fks_status fks_check_config_collision_device(fks_context* ctx, const double* d_c
     const uint32_t grid = (uint32_t)((groups_needed < (uint64_t)ctx->grid_groups) ? groups_needed : ctx->grid_groups);
     /* a batch larger than the resident grid runs the robot's shape-specialised check (built
      * here if the simulation has not built the module yet; a failure keeps the generic one) */
-    if (ctx->spec_pending && n > (uint64_t)ctx->grid_waves) {
-        ctx->spec_pending = false;
-        const std::string keep = ctx->last_error;
-        if (spec_prepare(ctx) != FKS_OK) ctx->last_error = keep + (keep.empty() ? "" : "; ") + ctx->last_error;
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-    }
+    if (ctx->spec.pending && n > (uint64_t)ctx->grid_waves) shaped_build_pending(ctx, &ctx->spec, kPlainModule);
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    if (ctx->spec_check_fn) {
+    if (ctx->spec.check_fn) {
         const fksd::SimArgs* argp = ctx->d_args;
         void* params[] = {&argp};
-        HIP_TRY(ctx, hipModuleLaunchKernel(ctx->spec_check_fn, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes,
+        HIP_TRY(ctx, hipModuleLaunchKernel(ctx->spec.check_fn, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes,
                                            s, params, nullptr));
         ctx->last_check_kernel = FKS_KERNEL_SHAPED;
     } else {
-        hipLaunchKernelGGL(check_kernel_for(ctx->R.type), dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s,
+        hipLaunchKernelGGL(kernel_of(KF_CHECK, false, ctx->R.type), dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s,
                            static_cast<const fksd::SimArgs*>(ctx->d_args));
         ctx->last_check_kernel = FKS_KERNEL_THROUGHPUT;
     }
@@ -1994,7 +1712,7 @@ static fks_status simulate_host(fks_context* ctx, const double* starts, uint64_t
     if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
     if (n > 0 && (!starts || !targets || !out_positions)) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "null host buffer");
     if (n > 0 && num_targets != 1 && num_targets != n)
-        return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "targets must be 1 or n (SPCS:792)");
+        return fail(ctx, FKS_ERR_INVALID_ARGUMENT, fks_batch::kTargetsOneOrN);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     fks_status st = settle(ctx);
     if (st != FKS_OK) return st;
@@ -2028,8 +1746,12 @@ static fks_status simulate_host(fks_context* ctx, const double* starts, uint64_t
         }
         HIP_TRY(ctx, hipMemcpy(ctx->d_pid, controller_state, pid_words * sizeof(double), hipMemcpyHostToDevice));
     }
-    st = simulate_device(ctx, ctx->d_starts, n, ctx->d_targets, nt, 0, allow_contacts, ctx->d_out, ctx->d_coll, ctx->d_micro,
-                         ctx->d_res, ctx->d_err, nullptr, 1, tr, controller_state ? ctx->d_pid : nullptr);
+    SimRequest rq;
+    rq.plain = plain_call(ctx->d_starts, n, ctx->d_targets, nt, 0, allow_contacts, ctx->d_out, ctx->d_coll, ctx->d_micro, ctx->d_res,
+                          ctx->d_err);
+    rq.trace = tr;
+    rq.d_pid_io = controller_state ? ctx->d_pid : nullptr;
+    st = simulate_device(ctx, rq);
     if (st != FKS_OK) return st;
     if (controller_state)
         HIP_TRY(ctx, hipMemcpy(controller_state, ctx->d_pid, pid_words * sizeof(double), hipMemcpyDeviceToHost));
@@ -2069,14 +1791,28 @@ fks_status fks_forward_simulate_mutable(fks_context* ctx, const double* starts, 
                          out_resolver_iterations, out_error_flags, nullptr, controller_state);
 }
 
-/* what both path entries refuse before anything is staged or counted */
-static fks_status path_arguments(fks_context* ctx, uint64_t num_legs) {
+/* What every batched entry does before anything is staged or counted: the refusals of its
+ * arguments (fks_batch::check_arguments) and the plan of its launch on this context */
+static fks_status plan_entry(fks_context* ctx, fks_batch::Inputs* in, fks_batch::Batch* b) {
     if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
     if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
-    if (num_legs == 0) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "a path needs at least one leg");
-    if (ctx->individual_jacobians)
-        return fail(ctx, FKS_ERR_UNSUPPORTED, "no path kernel with individual Jacobians (fks_set_individual_jacobians): chain plain calls");
-    return FKS_OK;
+    std::string why;
+    fks_status st = fks_batch::check_arguments(b, ctx->individual_jacobians != 0, &why);
+    if (st == FKS_OK) {
+        plan_inputs(ctx, in);
+        st = fks_batch::plan_batch(*in, b, &why);
+    }
+    return st == FKS_OK ? FKS_OK : fail(ctx, st, why);
+}
+
+static fks_status run_batch(fks_context* ctx, const fks_batch::Inputs& in, const fks_batch::Batch& b, void* stream,
+                            int32_t synchronize) {
+    SimRequest rq;
+    rq.batch = &b;
+    rq.inputs = &in;
+    rq.stream = stream;
+    rq.synchronize = synchronize;
+    return simulate_device(ctx, rq);
 }
 
 fks_status fks_forward_simulate_path_device(fks_context* ctx, const double* d_starts, uint64_t n, const double* d_waypoints,
@@ -2084,28 +1820,31 @@ fks_status fks_forward_simulate_path_device(fks_context* ctx, const double* d_st
                                             int32_t allow_contacts, double* d_out_positions, uint8_t* d_out_collided,
                                             uint32_t* d_out_microsteps, uint32_t* d_out_resolver_iterations,
                                             uint32_t* d_out_error_flags, void* stream, int32_t synchronize) {
-    const fks_status st = path_arguments(ctx, num_legs);
+    fks_batch::Inputs in;
+    fks_batch::Batch b;
+    fks_batch::from_path(&b, fks_batch::ENTRY_PATH_DEVICE, d_starts, n, d_waypoints, num_legs, num_targets, first_particle_id,
+                         allow_contacts, d_out_positions, d_out_collided, d_out_microsteps, d_out_resolver_iterations,
+                         d_out_error_flags);
+    const fks_status st = plan_entry(ctx, &in, &b);
     if (st != FKS_OK) return st;
-    return simulate_device(ctx, d_starts, n, d_waypoints, num_targets, first_particle_id, allow_contacts, d_out_positions,
-                           d_out_collided, d_out_microsteps, d_out_resolver_iterations, d_out_error_flags, stream, synchronize,
-                           nullptr, nullptr, num_legs);
+    return run_batch(ctx, in, b, stream, synchronize);
 }
 
+/* Copies straight between the caller's arrays and the staging buffers of the plain host calls
+ * (a path's arrays are one block each: the jobs' intermediate host buffer would only add a copy) */
 fks_status fks_forward_simulate_path(fks_context* ctx, const double* starts, uint64_t n, const double* waypoints, uint64_t num_legs,
                                      uint64_t num_targets, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
                                      uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags) {
-    fks_status st = path_arguments(ctx, num_legs);
+    fks_batch::Inputs in;
+    fks_batch::Batch b;
+    fks_batch::from_path(&b, fks_batch::ENTRY_PATH_HOST, starts, n, waypoints, num_legs, num_targets, 0, allow_contacts, out_positions,
+                         out_collided, out_microsteps, out_resolver_iterations, out_error_flags);
+    fks_status st = plan_entry(ctx, &in, &b);
     if (st != FKS_OK) return st;
-    if (n > 0 && (!starts || !waypoints || !out_positions)) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "null host buffer");
-    if (n > 0 && num_targets != 1 && num_targets != n)
-        return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "waypoints must hold 1 or n configurations per leg (SPCS:792)");
-    if (n > 0xffffffffull || num_legs >= (1ull << 31)) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "path too large");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     st = settle(ctx);
     if (st != FKS_OK) return st;
-    if (n == 0)
-        return simulate_device(ctx, nullptr, 0, nullptr, 0, 0, allow_contacts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1,
-                               nullptr, nullptr, num_legs);
+    if (n == 0) return run_batch(ctx, in, b, nullptr, 1);
     /* the staging buffers of the plain host calls, sized for the leg-major outputs */
     const size_t W = (size_t)ctx->R.W;
     const uint64_t rows = n * num_legs, nt = num_targets * num_legs;
@@ -2124,8 +1863,15 @@ fks_status fks_forward_simulate_path(fks_context* ctx, const double* starts, uin
     }
     HIP_TRY(ctx, hipMemcpy(ctx->d_starts, starts, n * W * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_targets, waypoints, nt * W * sizeof(double), hipMemcpyHostToDevice));
-    st = simulate_device(ctx, ctx->d_starts, n, ctx->d_targets, num_targets, 0, allow_contacts, ctx->d_out, ctx->d_coll, ctx->d_micro,
-                         ctx->d_res, ctx->d_err, nullptr, 1, nullptr, nullptr, num_legs);
+    fks_path_job& dev = b.converted[0]; /* the same path over the staging buffers */
+    dev.starts = ctx->d_starts;
+    dev.waypoints = ctx->d_targets;
+    dev.out_positions = ctx->d_out;
+    dev.out_collided = ctx->d_coll;
+    dev.out_microsteps = ctx->d_micro;
+    dev.out_resolver_iterations = ctx->d_res;
+    dev.out_error_flags = ctx->d_err;
+    st = run_batch(ctx, in, b, nullptr, 1);
     if (st != FKS_OK) return st;
     HIP_TRY(ctx, hipMemcpy(out_positions, ctx->d_out, rows * W * sizeof(double), hipMemcpyDeviceToHost));
     if (out_collided) HIP_TRY(ctx, hipMemcpy(out_collided, ctx->d_coll, rows, hipMemcpyDeviceToHost));
@@ -2137,188 +1883,20 @@ fks_status fks_forward_simulate_path(fks_context* ctx, const double* starts, uin
     return FKS_OK;
 }
 
-/* what both jobs entries refuse before anything is staged or counted; *total: the sum of n */
-static fks_status jobs_arguments(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs, uint64_t* total) {
-    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
-    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
-    if (num_jobs == 0 || !jobs) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "a job batch needs at least one job");
-    if (num_jobs > FKS_MAX_JOBS) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 65536 jobs per batch");
-    if (ctx->individual_jacobians)
-        return fail(ctx, FKS_ERR_UNSUPPORTED, "no jobs kernel with individual Jacobians (fks_set_individual_jacobians): issue plain calls");
-    uint64_t sum = 0;
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        const fks_job& job = jobs[j];
-        if (job.num_targets != 1 && job.num_targets != job.n)
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": targets must be 1 or n (SPCS:792)");
-        if (job.n > 0 && (!job.starts || !job.targets || !job.out_positions))
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": null starts, targets or out_positions");
-        if (job.n > 0xffffffffull || sum + job.n > 0xffffffffull)
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per batch");
-        sum += job.n;
-    }
-    *total = sum;
-    return FKS_OK;
-}
-
-fks_status fks_forward_simulate_jobs_device(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs, void* stream,
-                                            int32_t synchronize) {
-    uint64_t total = 0;
-    const fks_status st = jobs_arguments(ctx, jobs, num_jobs, &total);
-    if (st != FKS_OK) return st;
-    return simulate_device(ctx, nullptr, total, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, stream, synchronize,
-                           nullptr, nullptr, 0, jobs, num_jobs);
-}
-
-fks_status fks_forward_simulate_jobs(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs) {
-    uint64_t N = 0;
-    fks_status st = jobs_arguments(ctx, jobs, num_jobs, &N);
-    if (st != FKS_OK) return st;
+/* fks_forward_simulate_jobs and _path_jobs over host arrays: the batch's inputs go up in one
+ * copy (the staging buffers of the plain host calls: d_starts holds every job's starts and then
+ * every job's waypoints), the outputs are the jobs' leg-major blocks one behind the other
+ * (b.rows rows; a job's block is one row block), each array comes down in one copy and each
+ * job's block goes to its own arrays */
+static fks_status simulate_batch_host(fks_context* ctx, const fks_batch::Inputs& in, const fks_batch::Batch& b) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = settle(ctx);
+    fks_status st = settle(ctx);
     if (st != FKS_OK) return st;
-    if (N == 0) return simulate_device(ctx, nullptr, 0, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1,
-                                       nullptr, nullptr, 0, jobs, num_jobs);
-    /* the staging buffers of the plain host calls: d_starts holds every job's starts and then
-     * every job's targets, so the inputs go up in one copy */
+    if (b.total == 0) return run_batch(ctx, in, b, nullptr, 1);
     const size_t W = (size_t)ctx->R.W;
+    const uint64_t N = b.total, R = b.rows;
     uint64_t NT = 0;
-    for (uint64_t j = 0; j < num_jobs; ++j) NT += jobs[j].n > 0 ? jobs[j].num_targets : 0;
-    const uint64_t rows = N + NT;
-    if (rows > ctx->cap_particles) {
-        HIP_TRY(ctx, ensure(&ctx->d_starts, rows * W));
-        HIP_TRY(ctx, ensure(&ctx->d_out, rows * W));
-        HIP_TRY(ctx, ensure(&ctx->d_coll, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_micro, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_res, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_err, rows));
-        ctx->cap_particles = rows;
-    }
-    const size_t in_bytes = rows * W * sizeof(double);
-    const size_t q_bytes = N * W * sizeof(double), u_bytes = N * sizeof(uint32_t);
-    ctx->jobs_stage.resize(std::max(in_bytes, q_bytes + 3 * u_bytes + N));
-    double* h_in = reinterpret_cast<double*>(ctx->jobs_stage.data());
-    std::vector<fks_job> dev(jobs, jobs + num_jobs); /* the same jobs over the staging buffers */
-    uint64_t at = 0, tat = N;
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        fks_job& d = dev[j];
-        if (d.n == 0) continue;
-        std::memcpy(h_in + at * W, d.starts, d.n * W * sizeof(double));
-        std::memcpy(h_in + tat * W, d.targets, d.num_targets * W * sizeof(double));
-        d.starts = ctx->d_starts + at * W;
-        d.targets = ctx->d_starts + tat * W;
-        d.out_positions = ctx->d_out + at * W;
-        d.out_collided = ctx->d_coll + at;
-        d.out_microsteps = ctx->d_micro + at;
-        d.out_resolver_iterations = ctx->d_res + at;
-        d.out_error_flags = ctx->d_err + at;
-        at += d.n;
-        tat += d.num_targets;
-    }
-    HIP_TRY(ctx, hipMemcpy(ctx->d_starts, h_in, in_bytes, hipMemcpyHostToDevice));
-    st = simulate_device(ctx, nullptr, N, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, 0,
-                         dev.data(), num_jobs);
-    if (st != FKS_OK) return st;
-    /* one copy down per output array, then each job's rows to its own arrays */
-    double* h_q = reinterpret_cast<double*>(ctx->jobs_stage.data());
-    uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + N * W);
-    uint32_t* h_res = h_micro + N;
-    uint32_t* h_err = h_res + N;
-    uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + N);
-    bool want_coll = false, want_micro = false, want_res = false, want_err = false;
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        if (jobs[j].n == 0) continue;
-        want_coll |= jobs[j].out_collided != nullptr;
-        want_micro |= jobs[j].out_microsteps != nullptr;
-        want_res |= jobs[j].out_resolver_iterations != nullptr;
-        want_err |= jobs[j].out_error_flags != nullptr;
-    }
-    HIP_TRY(ctx, hipMemcpy(h_q, ctx->d_out, q_bytes, hipMemcpyDeviceToHost));
-    if (want_coll) HIP_TRY(ctx, hipMemcpy(h_coll, ctx->d_coll, N, hipMemcpyDeviceToHost));
-    if (want_micro) HIP_TRY(ctx, hipMemcpy(h_micro, ctx->d_micro, u_bytes, hipMemcpyDeviceToHost));
-    if (want_res) HIP_TRY(ctx, hipMemcpy(h_res, ctx->d_res, u_bytes, hipMemcpyDeviceToHost));
-    if (want_err) HIP_TRY(ctx, hipMemcpy(h_err, ctx->d_err, u_bytes, hipMemcpyDeviceToHost));
-    at = 0;
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        const fks_job& job = jobs[j];
-        if (job.n == 0) continue;
-        std::memcpy(job.out_positions, h_q + at * W, job.n * W * sizeof(double));
-        if (job.out_collided) std::memcpy(job.out_collided, h_coll + at, job.n);
-        if (job.out_microsteps) std::memcpy(job.out_microsteps, h_micro + at, job.n * sizeof(uint32_t));
-        if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations, h_res + at, job.n * sizeof(uint32_t));
-        if (job.out_error_flags) std::memcpy(job.out_error_flags, h_err + at, job.n * sizeof(uint32_t));
-        at += job.n;
-    }
-    ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
-    return FKS_OK;
-}
-
-}  // extern "C"
-
-/* what both path-jobs entries refuse before anything is staged or counted; *total: the sum of n,
- * *rows: the sum of n x num_legs (the rows of a leg-major output array) */
-static fks_status path_jobs_arguments(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs, uint64_t* total, uint64_t* rows) {
-    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
-    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
-    if (num_jobs == 0 || !jobs) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "a path-job batch needs at least one job");
-    if (num_jobs > FKS_MAX_JOBS) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 65536 jobs per batch");
-    if (ctx->individual_jacobians)
-        return fail(ctx, FKS_ERR_UNSUPPORTED,
-                    "no path-jobs kernel with individual Jacobians (fks_set_individual_jacobians): issue plain calls");
-    uint64_t sum = 0, legs = 0, max_legs = 0, r = 0;
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        const fks_path_job& job = jobs[j];
-        if (job.num_legs == 0) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": a path needs at least one leg");
-        if (job.num_legs > FKS_MAX_PATH_JOB_LEGS || legs + job.num_legs > FKS_MAX_PATH_JOB_LEGS)
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 65536 legs per batch (the sum of num_legs)");
-        if (job.num_targets != 1 && job.num_targets != job.n)
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT,
-                        "job " + std::to_string(j) + ": waypoints must hold 1 or n configurations per leg (SPCS:792)");
-        if (job.n > 0 && (!job.starts || !job.waypoints || !job.out_positions))
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": null starts, waypoints or out_positions");
-        if (job.n > 0xffffffffull || sum + job.n > 0xffffffffull)
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per batch");
-        sum += job.n;
-        legs += job.num_legs;
-        max_legs = std::max(max_legs, job.num_legs);
-        r += job.n * job.num_legs; /* < 2^32 x 2^16 */
-    }
-    /* seg_done counts the longest job's legs x segments per leg in 31 bits (simulate_device's rule) */
-    const uint32_t T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
-    const uint32_t k = std::min(ctx->segment_steps ? ctx->segment_steps : kDefaultSegmentSteps, T);
-    const bool segmented = ctx->segment_steps != 0 || sum > (uint64_t)ctx->grid_waves;
-    const uint64_t nseg = segmented ? ((uint64_t)T - 1u) / k + 1u : 1u;
-    if (max_legs * nseg >= (1ull << 31)) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "legs x segments per leg must stay below 2^31");
-    *total = sum;
-    *rows = r;
-    return FKS_OK;
-}
-
-extern "C" {
-
-fks_status fks_forward_simulate_path_jobs_device(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs, void* stream,
-                                                 int32_t synchronize) {
-    uint64_t total = 0, rows = 0;
-    const fks_status st = path_jobs_arguments(ctx, jobs, num_jobs, &total, &rows);
-    if (st != FKS_OK) return st;
-    return simulate_device(ctx, nullptr, total, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, stream, synchronize,
-                           nullptr, nullptr, 0, nullptr, num_jobs, jobs);
-}
-
-fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs) {
-    uint64_t N = 0, R = 0;
-    fks_status st = path_jobs_arguments(ctx, jobs, num_jobs, &N, &R);
-    if (st != FKS_OK) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = settle(ctx);
-    if (st != FKS_OK) return st;
-    if (N == 0) return simulate_device(ctx, nullptr, 0, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1,
-                                       nullptr, nullptr, 0, nullptr, num_jobs, jobs);
-    /* the staging buffers of the plain host calls: d_starts holds every job's starts and then
-     * every job's waypoints, so the inputs go up in one copy; the outputs are the jobs' leg-major
-     * blocks one behind the other (R = sum of n x num_legs rows) */
-    const size_t W = (size_t)ctx->R.W;
-    uint64_t NT = 0;
-    for (uint64_t j = 0; j < num_jobs; ++j) NT += jobs[j].n > 0 ? jobs[j].num_targets * jobs[j].num_legs : 0;
+    for (uint64_t j = 0; j < b.num_jobs; ++j) NT += b.jobs()[j].n > 0 ? b.jobs()[j].num_targets * b.jobs()[j].num_legs : 0;
     const uint64_t rows = std::max(N + NT, R);
     if (rows > ctx->cap_particles) {
         HIP_TRY(ctx, ensure(&ctx->d_starts, rows * W));
@@ -2333,10 +1911,10 @@ fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* 
     const size_t q_bytes = R * W * sizeof(double), u_bytes = R * sizeof(uint32_t);
     ctx->jobs_stage.resize(std::max(in_bytes, q_bytes + 3 * u_bytes + R));
     double* h_in = reinterpret_cast<double*>(ctx->jobs_stage.data());
-    std::vector<fks_path_job> dev(jobs, jobs + num_jobs); /* the same jobs over the staging buffers */
+    fks_batch::Batch dev = b; /* the same jobs over the staging buffers */
+    dev.converted.assign(b.jobs(), b.jobs() + b.num_jobs);
     uint64_t at = 0, tat = N, oat = 0;
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        fks_path_job& d = dev[j];
+    for (fks_path_job& d : dev.converted) {
         if (d.n == 0) continue;
         const uint64_t nt = d.num_targets * d.num_legs;
         std::memcpy(h_in + at * W, d.starts, d.n * W * sizeof(double));
@@ -2353,22 +1931,21 @@ fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* 
         oat += d.n * d.num_legs;
     }
     HIP_TRY(ctx, hipMemcpy(ctx->d_starts, h_in, in_bytes, hipMemcpyHostToDevice));
-    st = simulate_device(ctx, nullptr, N, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, 0,
-                         nullptr, num_jobs, dev.data());
+    st = run_batch(ctx, in, dev, nullptr, 1);
     if (st != FKS_OK) return st;
-    /* one copy down per output array, then each job's leg-major block to its own arrays */
     double* h_q = reinterpret_cast<double*>(ctx->jobs_stage.data());
     uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + R * W);
     uint32_t* h_res = h_micro + R;
     uint32_t* h_err = h_res + R;
     uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + R);
     bool want_coll = false, want_micro = false, want_res = false, want_err = false;
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        if (jobs[j].n == 0) continue;
-        want_coll |= jobs[j].out_collided != nullptr;
-        want_micro |= jobs[j].out_microsteps != nullptr;
-        want_res |= jobs[j].out_resolver_iterations != nullptr;
-        want_err |= jobs[j].out_error_flags != nullptr;
+    for (uint64_t j = 0; j < b.num_jobs; ++j) {
+        const fks_path_job& job = b.jobs()[j];
+        if (job.n == 0) continue;
+        want_coll |= job.out_collided != nullptr;
+        want_micro |= job.out_microsteps != nullptr;
+        want_res |= job.out_resolver_iterations != nullptr;
+        want_err |= job.out_error_flags != nullptr;
     }
     HIP_TRY(ctx, hipMemcpy(h_q, ctx->d_out, q_bytes, hipMemcpyDeviceToHost));
     if (want_coll) HIP_TRY(ctx, hipMemcpy(h_coll, ctx->d_coll, R, hipMemcpyDeviceToHost));
@@ -2376,8 +1953,8 @@ fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* 
     if (want_res) HIP_TRY(ctx, hipMemcpy(h_res, ctx->d_res, u_bytes, hipMemcpyDeviceToHost));
     if (want_err) HIP_TRY(ctx, hipMemcpy(h_err, ctx->d_err, u_bytes, hipMemcpyDeviceToHost));
     oat = 0;
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        const fks_path_job& job = jobs[j];
+    for (uint64_t j = 0; j < b.num_jobs; ++j) {
+        const fks_path_job& job = b.jobs()[j];
         if (job.n == 0) continue;
         const uint64_t r = job.n * job.num_legs;
         std::memcpy(job.out_positions, h_q + oat * W, r * W * sizeof(double));
@@ -2389,6 +1966,44 @@ fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* 
     }
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
     return FKS_OK;
+}
+
+fks_status fks_forward_simulate_jobs_device(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs, void* stream,
+                                            int32_t synchronize) {
+    fks_batch::Inputs in;
+    fks_batch::Batch b;
+    fks_batch::from_jobs(&b, jobs, num_jobs);
+    const fks_status st = plan_entry(ctx, &in, &b);
+    if (st != FKS_OK) return st;
+    return run_batch(ctx, in, b, stream, synchronize);
+}
+
+fks_status fks_forward_simulate_jobs(fks_context* ctx, const fks_job* jobs, uint64_t num_jobs) {
+    fks_batch::Inputs in;
+    fks_batch::Batch b;
+    fks_batch::from_jobs(&b, jobs, num_jobs);
+    const fks_status st = plan_entry(ctx, &in, &b);
+    if (st != FKS_OK) return st;
+    return simulate_batch_host(ctx, in, b);
+}
+
+fks_status fks_forward_simulate_path_jobs_device(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs, void* stream,
+                                                 int32_t synchronize) {
+    fks_batch::Inputs in;
+    fks_batch::Batch b;
+    fks_batch::from_path_jobs(&b, jobs, num_jobs);
+    const fks_status st = plan_entry(ctx, &in, &b);
+    if (st != FKS_OK) return st;
+    return run_batch(ctx, in, b, stream, synchronize);
+}
+
+fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs) {
+    fks_batch::Inputs in;
+    fks_batch::Batch b;
+    fks_batch::from_path_jobs(&b, jobs, num_jobs);
+    const fks_status st = plan_entry(ctx, &in, &b);
+    if (st != FKS_OK) return st;
+    return simulate_batch_host(ctx, in, b);
 }
 
 }  // extern "C"
@@ -2679,13 +2294,13 @@ fks_status fks_set_specialization(fks_context* ctx, int32_t mode) {
     fks_status st = settle(ctx);
     if (st != FKS_OK) return st;
     ctx->specialize = mode;
-    ctx->spec_pending = false;
+    ctx->spec.pending = false;
     /* the batched module is released with the plain one and, when the mode allows it, built
      * again at the first batch that runs it (or by fks_prepare_batched_specialization): this
      * call compiles the plain module only */
-    bspec_release(ctx);
-    ctx->bspec_pending = mode == FKS_SPECIALIZE_ON && ctx->has_robot;
-    return spec_prepare(ctx); /* now, for the current robot (releases it when disabled) */
+    shaped_release(ctx, &ctx->bspec);
+    ctx->bspec.pending = mode == FKS_SPECIALIZE_ON && ctx->has_robot;
+    return shaped_prepare(ctx, &ctx->spec, kPlainModule); /* now, for the current robot (releases it when disabled) */
 }
 
 fks_status fks_prepare_batched_specialization(fks_context* ctx) {
@@ -2697,9 +2312,9 @@ fks_status fks_prepare_batched_specialization(fks_context* ctx) {
     const fks_status st = settle(ctx);
     if (st != FKS_OK) return st;
     ctx->bspec_enabled = 1;
-    ctx->bspec_pending = false;
-    if (ctx->bspec_fn) return FKS_OK; /* built already */
-    return bspec_prepare(ctx);
+    ctx->bspec.pending = false;
+    if (ctx->bspec.fn) return FKS_OK; /* built already */
+    return shaped_prepare(ctx, &ctx->bspec, kBatchedModule);
 }
 
 fks_status fks_set_batched_specialization(fks_context* ctx, int32_t enabled) {
@@ -2708,34 +2323,28 @@ fks_status fks_set_batched_specialization(fks_context* ctx, int32_t enabled) {
     return FKS_OK;
 }
 
+static fks_status shaped_info(fks_specialization_info* out, int32_t enabled, bool pending, const ShapedModule& m) {
+    std::memset(out, 0, sizeof(*out));
+    out->enabled = enabled;
+    out->active = m.fn ? 1 : 0;
+    out->pending = pending ? 1 : 0;
+    out->from_cache = m.from_cache;
+    out->compile_seconds = m.seconds;
+    out->launches = m.launches;
+    std::snprintf(out->shape, sizeof(out->shape), "%s", m.shape.c_str());
+    out->failed = m.failed ? 1 : 0;
+    std::snprintf(out->message, sizeof(out->message), "%s", m.message.c_str());
+    return FKS_OK;
+}
+
 fks_status fks_get_batched_specialization(const fks_context* ctx, fks_specialization_info* out) {
     if (!ctx || !out) return FKS_ERR_INVALID_ARGUMENT;
-    std::memset(out, 0, sizeof(*out));
-    out->enabled = ctx->bspec_enabled;
-    out->active = ctx->bspec_fn ? 1 : 0;
-    out->pending = ctx->bspec_pending && ctx->bspec_enabled ? 1 : 0;
-    out->from_cache = ctx->bspec_from_cache;
-    out->compile_seconds = ctx->bspec_seconds;
-    out->launches = ctx->bspec_launches;
-    std::snprintf(out->shape, sizeof(out->shape), "%s", ctx->bspec_shape.c_str());
-    out->failed = ctx->bspec_failed ? 1 : 0;
-    std::snprintf(out->message, sizeof(out->message), "%s", ctx->bspec_message.c_str());
-    return FKS_OK;
+    return shaped_info(out, ctx->bspec_enabled, ctx->bspec.pending && ctx->bspec_enabled, ctx->bspec);
 }
 
 fks_status fks_get_specialization(const fks_context* ctx, fks_specialization_info* out) {
     if (!ctx || !out) return FKS_ERR_INVALID_ARGUMENT;
-    std::memset(out, 0, sizeof(*out));
-    out->enabled = ctx->specialize;
-    out->active = ctx->spec_fn ? 1 : 0;
-    out->pending = ctx->spec_pending ? 1 : 0;
-    out->from_cache = ctx->spec_from_cache;
-    out->compile_seconds = ctx->spec_seconds;
-    out->launches = ctx->spec_launches;
-    std::snprintf(out->shape, sizeof(out->shape), "%s", ctx->spec_shape.c_str());
-    out->failed = ctx->spec_failed ? 1 : 0;
-    std::snprintf(out->message, sizeof(out->message), "%s", ctx->spec_message.c_str());
-    return FKS_OK;
+    return shaped_info(out, ctx->specialize, ctx->spec.pending, ctx->spec);
 }
 
 fks_status fks_get_launch_geometry(const fks_context* ctx, uint32_t* resident_waves, uint64_t* lds_bytes_per_group) {

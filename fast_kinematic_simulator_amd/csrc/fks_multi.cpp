@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "fks_capi.h"
+#include "fks_batch.h"
 
 struct fks_multi_context {
     struct Device {
@@ -221,7 +222,7 @@ static fks_status multi_simulate(fks_multi_context* m, const double* starts, uin
     if (!m) return FKS_ERR_INVALID_ARGUMENT;
     if (m->width <= 0) return mfail(m, FKS_ERR_NO_ROBOT, "fks_multi_set_robot has not been called");
     if (n > 0 && (!starts || !targets || !out_positions)) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "null host buffer");
-    if (n > 0 && num_targets != 1 && num_targets != n) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "targets must be 1 or n (SPCS:792)");
+    if (n > 0 && num_targets != 1 && num_targets != n) return mfail(m, FKS_ERR_INVALID_ARGUMENT, fks_batch::kTargetsOneOrN);
     const auto t0 = std::chrono::steady_clock::now();
     const size_t W = (size_t)m->width;
     const int32_t ndev = active_count(m);
@@ -344,157 +345,20 @@ fks_status fks_multi_forward_simulate_path(fks_multi_context* m, const double* s
                           out_microsteps, out_resolver_iterations, out_error_flags);
 }
 
-fks_status fks_multi_forward_simulate_jobs(fks_multi_context* m, const fks_job* jobs, uint64_t num_jobs) {
+/* fks_multi_forward_simulate_jobs and _path_jobs: the batch in its normal form (fks_batch.h: a job
+ * is a path job of one leg), the concatenated particle range cut into one shard per device, and
+ * each shard run through the entry's own device call, so it runs the kernels of its own form */
+static fks_status multi_batch(fks_multi_context* m, fks_batch::Batch& b) {
     if (!m) return FKS_ERR_INVALID_ARGUMENT;
     if (m->width <= 0) return mfail(m, FKS_ERR_NO_ROBOT, "fks_multi_set_robot has not been called");
-    if (num_jobs == 0 || !jobs) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "a job batch needs at least one job");
-    if (num_jobs > FKS_MAX_JOBS) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "at most 65536 jobs per batch");
+    std::string why;
+    const fks_status refused = fks_batch::check_arguments(&b, /*individual_jacobians: the devices' contexts refuse*/ false, &why);
+    if (refused != FKS_OK) return mfail(m, refused, why);
+    const fks_path_job* jobs = b.jobs();
+    const uint64_t num_jobs = b.num_jobs;
     std::vector<uint64_t> first((size_t)num_jobs + 1, 0); /* the jobs' first particles in the concatenated range */
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        const fks_job& job = jobs[j];
-        if (job.num_targets != 1 && job.num_targets != job.n)
-            return mfail(m, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": targets must be 1 or n (SPCS:792)");
-        if (job.n > 0 && (!job.starts || !job.targets || !job.out_positions))
-            return mfail(m, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": null starts, targets or out_positions");
-        if (job.n > 0xffffffffull || first[j] + job.n > 0xffffffffull)
-            return mfail(m, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per batch");
-        first[j + 1] = first[j] + job.n;
-    }
-    const uint64_t N = first[num_jobs];
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t W = (size_t)m->width;
-    const int32_t ndev = active_count(m);
-    const uint64_t call = m->call_index;
-    /* one host thread per device: stage in, launch, stage out (the devices run concurrently) */
-    on_device_threads(ndev, [&](int32_t g) {
-        auto& d = m->devices[(size_t)g];
-        d.status = FKS_OK;
-        d.error.clear();
-        std::memset(&d.counters, 0, sizeof(d.counters));
-        uint64_t lo = 0, hi = 0;
-        fks_shard_bounds(N, ndev, g, &lo, &hi);
-        const uint64_t k = hi - lo;
-        /* the device's jobs: of every job the shard meets its rows [a, b), every other job empty */
-        std::vector<fks_job> dev((size_t)num_jobs);
-        std::vector<uint64_t> row0((size_t)num_jobs, 0); /* the sub-range's first row within its job */
-        uint64_t nt = 0;
-        for (uint64_t j = 0; j < num_jobs; ++j) {
-            const uint64_t a = std::max(first[j], lo), b = std::min(first[j + 1], hi);
-            fks_job& s = dev[j];
-            std::memset(&s, 0, sizeof(s));
-            s.num_targets = 1; /* an empty job: 1 is always accepted */
-            if (a >= b) continue;
-            row0[j] = a - first[j];
-            s.n = b - a;
-            s.num_targets = (jobs[j].num_targets == jobs[j].n && jobs[j].n != 1) ? s.n : 1;
-            s.first_particle_id = jobs[j].first_particle_id + row0[j];
-            s.allow_contacts = jobs[j].allow_contacts;
-            nt += s.num_targets;
-        }
-        DCTX(d, fks_set_call_index(d.ctx, call), "fks_set_call_index");
-        DHIP(d, hipSetDevice(d.device));
-        if (k > d.cap) {
-            DHIP(d, grow(&d.d_starts, k * W));
-            DHIP(d, grow(&d.d_out, k * W));
-            DHIP(d, grow(&d.d_coll, k));
-            DHIP(d, grow(&d.d_micro, k));
-            DHIP(d, grow(&d.d_res, k));
-            DHIP(d, grow(&d.d_err, k));
-            d.cap = k;
-        }
-        if (nt > d.cap_targets) {
-            DHIP(d, grow(&d.d_targets, nt * W));
-            d.cap_targets = nt;
-        }
-        const size_t in_bytes = (k + nt) * W * sizeof(double);
-        const size_t out_bytes = k * W * sizeof(double) + k * (1 + 3 * sizeof(uint32_t));
-        DHIP(d, grow_pinned(&d.h_in, &d.cap_h_in, in_bytes));
-        DHIP(d, grow_pinned(&d.h_out, &d.cap_h_out, out_bytes));
-        double* h_starts = reinterpret_cast<double*>(d.h_in);
-        double* h_targets = h_starts + k * W;
-        uint64_t at = 0, tat = 0;
-        for (uint64_t j = 0; j < num_jobs; ++j) {
-            fks_job& s = dev[j];
-            if (s.n == 0) continue;
-            std::memcpy(h_starts + at * W, jobs[j].starts + row0[j] * W, s.n * W * sizeof(double));
-            std::memcpy(h_targets + tat * W, jobs[j].targets + (s.num_targets == 1 && jobs[j].num_targets == 1 ? 0 : row0[j]) * W,
-                        s.num_targets * W * sizeof(double));
-            s.starts = d.d_starts + at * W;
-            s.targets = d.d_targets + tat * W;
-            s.out_positions = d.d_out + at * W;
-            s.out_collided = d.d_coll + at;
-            s.out_microsteps = d.d_micro + at;
-            s.out_resolver_iterations = d.d_res + at;
-            s.out_error_flags = d.d_err + at;
-            at += s.n;
-            tat += s.num_targets;
-        }
-        if (k > 0) {
-            DHIP(d, hipMemcpyAsync(d.d_starts, h_starts, k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
-            DHIP(d, hipMemcpyAsync(d.d_targets, h_targets, nt * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
-        }
-        DCTX(d, fks_forward_simulate_jobs_device(d.ctx, dev.data(), num_jobs, d.stream, 0), "fks_forward_simulate_jobs_device");
-        if (k == 0) {
-            DCTX(d, fks_get_last_call_counters(d.ctx, &d.counters), "fks_get_last_call_counters"); /* settles */
-            std::memset(&d.counters, 0, sizeof(d.counters));
-            return;
-        }
-        double* h_q = reinterpret_cast<double*>(d.h_out);
-        uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + k * W);
-        uint32_t* h_res = h_micro + k;
-        uint32_t* h_err = h_res + k;
-        uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + k);
-        DHIP(d, hipMemcpyAsync(h_q, d.d_out, k * W * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_micro, d.d_micro, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_res, d.d_res, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_err, d.d_err, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_coll, d.d_coll, k, hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipStreamSynchronize(d.stream));
-        at = 0;
-        for (uint64_t j = 0; j < num_jobs; ++j) {
-            const fks_job& s = dev[j];
-            const fks_job& job = jobs[j];
-            if (s.n == 0) continue;
-            const uint64_t dst = row0[j];
-            std::memcpy(job.out_positions + dst * W, h_q + at * W, s.n * W * sizeof(double));
-            if (job.out_collided) std::memcpy(job.out_collided + dst, h_coll + at, s.n);
-            if (job.out_microsteps) std::memcpy(job.out_microsteps + dst, h_micro + at, s.n * sizeof(uint32_t));
-            if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations + dst, h_res + at, s.n * sizeof(uint32_t));
-            if (job.out_error_flags) std::memcpy(job.out_error_flags + dst, h_err + at, s.n * sizeof(uint32_t));
-            at += s.n;
-        }
-        DCTX(d, fks_get_last_call_counters(d.ctx, &d.counters), "fks_get_last_call_counters"); /* settles the launch */
-    });
-    const fks_status st = collect_status(m, ndev);
-    if (st != FKS_OK) return st; /* a refusal by the devices' contexts leaves the call index where it was */
-    m->call_index = call + num_jobs;
-    sum_counters(m, ndev, t0);
-    return FKS_OK;
-}
-
-fks_status fks_multi_forward_simulate_path_jobs(fks_multi_context* m, const fks_path_job* jobs, uint64_t num_jobs) {
-    if (!m) return FKS_ERR_INVALID_ARGUMENT;
-    if (m->width <= 0) return mfail(m, FKS_ERR_NO_ROBOT, "fks_multi_set_robot has not been called");
-    if (num_jobs == 0 || !jobs) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "a path-job batch needs at least one job");
-    if (num_jobs > FKS_MAX_JOBS) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "at most 65536 jobs per batch");
-    std::vector<uint64_t> first((size_t)num_jobs + 1, 0); /* the jobs' first particles in the concatenated range */
-    uint64_t legs = 0;
-    for (uint64_t j = 0; j < num_jobs; ++j) {
-        const fks_path_job& job = jobs[j];
-        if (job.num_legs == 0) return mfail(m, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": a path needs at least one leg");
-        if (job.num_legs > FKS_MAX_PATH_JOB_LEGS || legs + job.num_legs > FKS_MAX_PATH_JOB_LEGS)
-            return mfail(m, FKS_ERR_INVALID_ARGUMENT, "at most 65536 legs per batch (the sum of num_legs)");
-        if (job.num_targets != 1 && job.num_targets != job.n)
-            return mfail(m, FKS_ERR_INVALID_ARGUMENT,
-                         "job " + std::to_string(j) + ": waypoints must hold 1 or n configurations per leg (SPCS:792)");
-        if (job.n > 0 && (!job.starts || !job.waypoints || !job.out_positions))
-            return mfail(m, FKS_ERR_INVALID_ARGUMENT, "job " + std::to_string(j) + ": null starts, waypoints or out_positions");
-        if (job.n > 0xffffffffull || first[j] + job.n > 0xffffffffull)
-            return mfail(m, FKS_ERR_INVALID_ARGUMENT, "at most 2^32-1 particles per batch");
-        first[j + 1] = first[j] + job.n;
-        legs += job.num_legs;
-    }
-    const uint64_t N = first[num_jobs];
+    for (uint64_t j = 0; j < num_jobs; ++j) first[j + 1] = first[j] + jobs[j].n;
+    const uint64_t N = b.total;
     const auto t0 = std::chrono::steady_clock::now();
     const size_t W = (size_t)m->width;
     const int32_t ndev = active_count(m);
@@ -514,14 +378,14 @@ fks_status fks_multi_forward_simulate_path_jobs(fks_multi_context* m, const fks_
         std::vector<uint64_t> row0((size_t)num_jobs, 0); /* the sub-range's first row within its job */
         uint64_t nt = 0, rows = 0; /* the shard's waypoint rows and leg-major output rows */
         for (uint64_t j = 0; j < num_jobs; ++j) {
-            const uint64_t a = std::max(first[j], lo), b = std::min(first[j + 1], hi);
+            const uint64_t a = std::max(first[j], lo), e = std::min(first[j + 1], hi);
             fks_path_job& s = dev[j];
             std::memset(&s, 0, sizeof(s));
             s.num_legs = jobs[j].num_legs;
             s.num_targets = 1; /* an empty job: 1 is always accepted */
-            if (a >= b) continue;
+            if (a >= e) continue;
             row0[j] = a - first[j];
-            s.n = b - a;
+            s.n = e - a;
             s.num_targets = (jobs[j].num_targets == jobs[j].n && jobs[j].n != 1) ? s.n : 1;
             s.first_particle_id = jobs[j].first_particle_id + row0[j];
             s.allow_contacts = jobs[j].allow_contacts;
@@ -574,8 +438,14 @@ fks_status fks_multi_forward_simulate_path_jobs(fks_multi_context* m, const fks_
             DHIP(d, hipMemcpyAsync(d.d_starts, h_starts, k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
             DHIP(d, hipMemcpyAsync(d.d_targets, h_targets, nt * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
         }
-        DCTX(d, fks_forward_simulate_path_jobs_device(d.ctx, dev.data(), num_jobs, d.stream, 0),
-             "fks_forward_simulate_path_jobs_device");
+        if (b.form == fks_batch::JOBS) {
+            std::vector<fks_job> as_jobs((size_t)num_jobs);
+            for (uint64_t j = 0; j < num_jobs; ++j) as_jobs[j] = fks_batch::as_job(dev[j]);
+            DCTX(d, fks_forward_simulate_jobs_device(d.ctx, as_jobs.data(), num_jobs, d.stream, 0), "fks_forward_simulate_jobs_device");
+        } else {
+            DCTX(d, fks_forward_simulate_path_jobs_device(d.ctx, dev.data(), num_jobs, d.stream, 0),
+                 "fks_forward_simulate_path_jobs_device");
+        }
         if (k == 0) {
             DCTX(d, fks_get_last_call_counters(d.ctx, &d.counters), "fks_get_last_call_counters"); /* settles */
             std::memset(&d.counters, 0, sizeof(d.counters));
@@ -611,9 +481,21 @@ fks_status fks_multi_forward_simulate_path_jobs(fks_multi_context* m, const fks_
     });
     const fks_status st = collect_status(m, ndev);
     if (st != FKS_OK) return st; /* a refusal by the devices' contexts leaves the call index where it was */
-    m->call_index = call + legs;
+    m->call_index = call + b.legs;  /* a job batch's jobs, a path-job batch's sum of legs */
     sum_counters(m, ndev, t0);
     return FKS_OK;
+}
+
+fks_status fks_multi_forward_simulate_jobs(fks_multi_context* m, const fks_job* jobs, uint64_t num_jobs) {
+    fks_batch::Batch b;
+    fks_batch::from_jobs(&b, jobs, num_jobs);
+    return multi_batch(m, b);
+}
+
+fks_status fks_multi_forward_simulate_path_jobs(fks_multi_context* m, const fks_path_job* jobs, uint64_t num_jobs) {
+    fks_batch::Batch b;
+    fks_batch::from_path_jobs(&b, jobs, num_jobs);
+    return multi_batch(m, b);
 }
 
 fks_status fks_multi_set_active_devices(fks_multi_context* m, int32_t count) {
