@@ -15,7 +15,15 @@ CASES = {
     "linked_cfg3": lambda: W.cfg3(16 / 65536),
     "linked_continuous": lambda: W.folding_arm(0.5, continuous=True),
     "dual_arm": lambda: W.cfg5(16 / 1048576),
+    "mixed_tree": lambda: _mixed_tree(),
 }
+
+
+def _mixed_tree():
+    """tests/joint_zoo.py: revolute, prismatic, fixed and continuous joints on a branched tree"""
+    import joint_zoo
+
+    return joint_zoo.mixed_tree()
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -34,6 +42,39 @@ def test_clean_steps_match_oracle(oracle_lib, name):
         assert np.array_equal(q, q_o[k]), k
     assert np.array_equal(r.controller_state, pid_o)
     assert np.any(q_o[-1] != wl.starts[0])
+
+
+def test_mixed_tree_steps_cover_the_prismatic_clamp_and_the_error_wrap(oracle_lib):
+    """The host entry points on the zoo's branched tree, bit for bit against the oracle, on a run
+    asserted to pass through both branches no other case reaches: a prismatic value clamped onto its
+    limit (ApplyControlInput, TNUVA:559) and a continuous dof's error wrapped the short way round
+    (GenerateControlAction's SignedDistance, TNUVA:603)."""
+    import oracle
+
+    wl = CASES["mixed_tree"]()
+    robot, start = wl.robot, wl.starts[0]
+    lo, hi = robot.dof_limits()
+    target = wl.targets[0].copy()
+    target[1] = 0.5  # past the prismatic upper limit 0.35
+    dt = 1.0 / wl.controller_frequency
+    u_o, q_o, pid_o = oracle.robot_steps(robot, start, target, dt, 40, 1)
+    r = RobotController(robot, start)
+    r.reset_position(start)
+    before = start
+    clamped = 0
+    for k in range(40):
+        u = r.generate_control_action(target, dt)
+        assert np.array_equal(u, u_o[k]), k
+        q = r.apply_control_input(u)
+        assert np.array_equal(q, q_o[k]), k
+        clamped += int(before[1] + u[1] > hi[1] and q[1] == hi[1])
+        before = q
+    assert np.array_equal(r.controller_state, pid_o)
+    assert clamped > 0
+    # dof 2 is continuous, starts near +2.9 and is sent to -2.9: the error is wrap(-5.8) > 0, the
+    # control drives it upwards and the value comes out beyond +pi at the negative end
+    assert target[2] < start[2] and u_o[0][2] > 0.0 and np.any(q_o[:, 2] < 0.0)
+    assert np.all(np.abs(q_o[:, 2]) <= np.pi)
 
 
 def test_noisy_step_stays_within_the_actuator_bound():
