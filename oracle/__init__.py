@@ -73,6 +73,8 @@ def _load(path):
         POINTER(C.Environment), POINTER(C.SolverParams), c_double, c_uint64, c_uint64, POINTER(C.RobotDesc),
         POINTER(c_double), c_uint64, POINTER(c_double), c_uint64, c_int32, c_int32, POINTER(c_double), POINTER(c_uint8),
         POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32), POINTER(C.Trace), c_uint64]
+    L.oracle_forward_simulate_traced_individual.restype = c_int32
+    L.oracle_forward_simulate_traced_individual.argtypes = L.oracle_forward_simulate_traced.argtypes + [c_int32]
     L.oracle_philox4x32_10.restype = None
     L.oracle_philox4x32_10.argtypes = [POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]
     L.oracle_pid_sequence.restype = None
@@ -156,8 +158,10 @@ def forward_simulate(env, robot, solver, frequency, seed, starts, targets, allow
 
 
 def forward_simulate_traced(env, robot, solver, frequency, seed, starts, targets, allow_contacts=True, call_index=0,
-                            step_capacity=None, config_capacity=4096, threads=0, first_particle_id=0):
+                            step_capacity=None, config_capacity=4096, threads=0, first_particle_id=0,
+                            individual_jacobians=False):
     """ForwardSimulateRobot with enable_tracing (SPCS:824-829) per particle, counter RNG.
+    individual_jacobians: the simulate_with_individual_jacobians constructor flag (SPCS:420).
     Returns (result dict, fast_kinematic_simulator_amd.trace.TraceBuffers)."""
     L = lib()
     from fast_kinematic_simulator_amd.trace import TraceBuffers
@@ -178,11 +182,12 @@ def forward_simulate_traced(env, robot, solver, frequency, seed, starts, targets
     micro = np.zeros(n, dtype=np.uint32)
     res = np.zeros(n, dtype=np.uint32)
     err = np.zeros(n, dtype=np.uint32)
-    st = L.oracle_forward_simulate_traced(ctypes.byref(env_c), ctypes.byref(params), float(frequency), c_uint64(int(seed)),
-                                          c_uint64(int(call_index)), ctypes.byref(desc), _p(starts, c_double), n,
-                                          _p(targets, c_double), targets.shape[0], 1 if allow_contacts else 0, int(threads),
-                                          _p(out, c_double), _p(coll, c_uint8), _p(micro, c_uint32), _p(res, c_uint32),
-                                          _p(err, c_uint32), ctypes.byref(tr), c_uint64(int(first_particle_id)))
+    args = [ctypes.byref(env_c), ctypes.byref(params), float(frequency), c_uint64(int(seed)), c_uint64(int(call_index)),
+            ctypes.byref(desc), _p(starts, c_double), n, _p(targets, c_double), targets.shape[0], 1 if allow_contacts else 0,
+            int(threads), _p(out, c_double), _p(coll, c_uint8), _p(micro, c_uint32), _p(res, c_uint32), _p(err, c_uint32),
+            ctypes.byref(tr), c_uint64(int(first_particle_id))]
+    # the stacked solve stays on the entry it always used (the sanitizer driver calls it too)
+    st = L.oracle_forward_simulate_traced_individual(*args, 1) if individual_jacobians else L.oracle_forward_simulate_traced(*args)
     del keep_env, keep_robot
     if st != 0:
         raise RuntimeError(f"oracle_forward_simulate_traced failed ({st})")

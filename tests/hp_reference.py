@@ -172,12 +172,14 @@ def link_path(robot, link):
     return path[::-1]
 
 
-def point_jacobian(robot, q, geometry, point, B=DEFAULT):
+def point_jacobian(robot, q, geometry, point, B=DEFAULT, T=None):
     """d(world position of `point` on geometry's link) / dq, 3 x D: a_w x (x - o_w) for revolute and
     continuous dofs, a_w for prismatic dofs, zero for the dofs off the link's path.  a_w is the
     joint axis as the description gives it (prismatic motion is axis * q, no normalisation) and, for
-    a rotation, its direction; o_w the joint frame's origin."""
-    T = link_transforms(robot, q, B)
+    a rotation, its direction; o_w the joint frame's origin.  T: link_transforms(robot, q, B), if the
+    caller has them already."""
+    if T is None:
+        T = link_transforms(robot, q, B)
     link = robot.geometry_link[geometry]
     p = B.array(point)
     x = (T[link] @ p)[:3]
@@ -272,8 +274,8 @@ def se3_jacobian(pose12, point, B=DEFAULT):
 def _velocity_clamp(robot, u, B):
     out = []
     for c, x in zip(robot.controllers, u):
-        lim = abs(c.velocity_limit)
-        out.append(B.scalar(min(max(float(x), -lim), lim)))  # a clamp of float64 values is exact
+        lim = B.scalar(abs(c.velocity_limit))
+        out.append(min(max(B.scalar(x), -lim), lim))  # a clamp rounds nothing: exact for float64 and backend inputs
     return out
 
 
