@@ -222,7 +222,27 @@ class LaunchInfo(ctypes.Structure):
 
 KERNEL_KINDS = {0: "none", 1: "throughput", 2: "small_batch", 3: "shaped", 4: "traced", 5: "individual", 6: "cooperative",
                 7: "shaped_small_batch", 8: "path", 9: "path_small_batch", 10: "jobs", 11: "jobs_small_batch",
-                12: "path_jobs", 13: "path_jobs_small_batch", 14: "shaped_path_jobs", 15: "shaped_path_jobs_small_batch"}
+                12: "path_jobs", 13: "path_jobs_small_batch", 14: "shaped_path_jobs", 15: "shaped_path_jobs_small_batch",
+                16: "policy", 17: "policy_small_batch"}
+
+# fks_policy_table verdicts and entry flags (include/fks_capi.h)
+POLICY_ENTRY_TERMINAL = 0x1
+POLICY_ARRIVED = 0x80000000
+POLICY_LOST = 0xFFFFFFFE
+POLICY_NONE = 0xFFFFFFFF
+
+
+class PolicyTable(ctypes.Structure):
+    """fks_policy_table: a policy's states (keys), actions (targets) and flags (host or device pointers, as the entry
+    takes them) with the two distances of the verdict."""
+    _fields_ = [
+        ("keys", c_void_p),
+        ("targets", c_void_p),
+        ("flags", c_void_p),
+        ("num_entries", c_uint64),
+        ("terminal_distance", c_double),
+        ("max_distance", c_double),
+    ]
 
 
 class Job(ctypes.Structure):
@@ -333,6 +353,20 @@ PROTOTYPES = [
         c_int32,
         [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_uint64, c_uint64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p, c_int32],
+    ),
+    ("fks_policy_select", c_int32, [POINTER(RobotDesc), POINTER(PolicyTable), POINTER(c_double), c_uint64, POINTER(c_uint32),
+                                    POINTER(c_double)]),
+    (
+        "fks_forward_simulate_policy",
+        c_int32,
+        [c_void_p, POINTER(c_double), c_uint64, POINTER(PolicyTable), c_uint64, c_int32, POINTER(c_double), POINTER(c_uint8),
+         POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32), POINTER(c_double), POINTER(c_uint32)],
+    ),
+    (
+        "fks_forward_simulate_policy_device",
+        c_int32,
+        [c_void_p, c_void_p, c_uint64, POINTER(PolicyTable), c_uint64, c_uint64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32],
     ),
     ("fks_forward_simulate_jobs", c_int32, [c_void_p, POINTER(Job), c_uint64]),
     ("fks_forward_simulate_jobs_device", c_int32, [c_void_p, POINTER(Job), c_uint64, c_void_p, c_int32]),

@@ -80,6 +80,21 @@ void from_path(Batch* b, Entry entry, const double* starts, uint64_t n, const do
     p.out_error_flags = out_error_flags;
 }
 
+void from_policy(Batch* b, Entry entry, const double* starts, uint64_t n, const fks_policy_table* table, uint64_t max_legs,
+                 uint64_t first_particle_id, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
+                 uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags, uint32_t* out_choice,
+                 double* out_distance, uint32_t* out_legs_run) {
+    /* a path whose legs' targets are chosen on the device: no waypoints, a target per particle */
+    from_path(b, entry, starts, n, nullptr, max_legs, n, first_particle_id, allow_contacts, out_positions, out_collided,
+              out_microsteps, out_resolver_iterations, out_error_flags);
+    b->policy = true;
+    b->has_table = table != nullptr;
+    if (table) b->table = *table;
+    b->out_choice = out_choice;
+    b->out_distance = out_distance;
+    b->out_legs_run = out_legs_run;
+}
+
 void from_jobs(Batch* b, const fks_job* jobs, uint64_t num_jobs) {
     b->form = JOBS;
     b->entry = ENTRY_JOBS;
@@ -144,6 +159,7 @@ struct Wording {
 };
 const char* const kWaypointsOneOrN = "waypoints must hold 1 or n configurations per leg (SPCS:792)";
 const char* const kNoPathKernel = "no path kernel with individual Jacobians (fks_set_individual_jacobians): chain plain calls";
+const char* const kNoPolicyKernel = "no policy kernel with individual Jacobians (fks_set_individual_jacobians): chain plain calls";
 const Wording kWording[] = {
     /* ENTRY_PATH_DEVICE */
     {nullptr, kNoPathKernel, kTargetsOneOrN, "null device buffer", "at most 2^32-1 particles per call", nullptr},
@@ -158,6 +174,12 @@ const Wording kWording[] = {
      "no path-jobs kernel with individual Jacobians (fks_set_individual_jacobians): issue plain calls",
      kWaypointsOneOrN, "null starts, waypoints or out_positions",
      "at most 2^32-1 particles per batch", nullptr},
+    /* ENTRY_POLICY_DEVICE */
+    {nullptr, kNoPolicyKernel, nullptr, "null device buffer (starts, out_positions or out_choice)",
+     "at most 2^32-1 particles per call", nullptr},
+    /* ENTRY_POLICY_HOST */
+    {nullptr, kNoPolicyKernel, nullptr, "null host buffer (starts, out_positions or out_choice)",
+     "at most 2^32-1 particles per call", "roll-out too large"},
 };
 
 fks_status refuse(std::string* why, fks_status st, std::string text) {
@@ -165,9 +187,32 @@ fks_status refuse(std::string* why, fks_status st, std::string text) {
     return st;
 }
 
+/* a roll-out's refusals: its legs, its table, its buffers, then its size */
+fks_status check_policy(Batch* b, bool individual_jacobians, std::string* why) {
+    const Wording& w = kWording[b->entry];
+    const fks_path_job& job = b->jobs()[0];
+    const fks_policy_table& t = b->table;
+    if (job.num_legs == 0) return refuse(why, FKS_ERR_INVALID_ARGUMENT, "a roll-out needs at least one leg (max_legs)");
+    if (individual_jacobians) return refuse(why, FKS_ERR_UNSUPPORTED, w.individual);
+    if (!b->has_table) return refuse(why, FKS_ERR_INVALID_ARGUMENT, "null policy table");
+    if (t.num_entries == 0) return refuse(why, FKS_ERR_INVALID_ARGUMENT, "a policy table needs at least one entry");
+    if (t.num_entries > FKS_MAX_POLICY_ENTRIES) return refuse(why, FKS_ERR_INVALID_ARGUMENT, "at most 2^30 policy entries");
+    if (!t.keys || !t.targets) return refuse(why, FKS_ERR_INVALID_ARGUMENT, "null policy keys or targets");
+    if (t.terminal_distance != t.terminal_distance || t.max_distance != t.max_distance)
+        return refuse(why, FKS_ERR_INVALID_ARGUMENT, "terminal_distance or max_distance is NaN");
+    if (job.n > 0 && (!job.starts || !job.out_positions || !b->out_choice)) return refuse(why, FKS_ERR_INVALID_ARGUMENT, w.null_buffer);
+    if (w.too_large && (job.n > 0xffffffffull || job.num_legs >= (1ull << 31))) return refuse(why, FKS_ERR_INVALID_ARGUMENT, w.too_large);
+    if (job.n > 0xffffffffull) return refuse(why, FKS_ERR_INVALID_ARGUMENT, w.particles);
+    b->total = job.n;
+    b->legs = b->max_legs = job.num_legs;
+    b->rows = job.n * job.num_legs;
+    return FKS_OK;
+}
+
 }  // namespace
 
 fks_status check_arguments(Batch* b, bool individual_jacobians, std::string* why) {
+    if (b->policy) return check_policy(b, individual_jacobians, why);
     const Wording& w = kWording[b->entry];
     const bool one_path = b->form == PATH; /* a path's checks name no job, and hold from one particle on */
     if (one_path) {
@@ -218,8 +263,11 @@ RecordPlan plan_records(const Batch& b) {
     /* the records are followed by job_first and leg_first [num_jobs + 1], in whole records */
     const size_t prefix = (2 * (size_t)(b.num_jobs + 1) * sizeof(uint32_t) + sizeof(fksd::SimArgs) - 1) / sizeof(fksd::SimArgs);
     r.records = (size_t)b.legs + prefix;
+    static_assert(sizeof(fksd::PolicyArgs) <= sizeof(fksd::SimArgs), "a roll-out's PolicyArgs takes one unit of the upload");
+    if (b.policy) r.policy_record = r.records++;
     r.call_advance = b.legs; /* a path's legs, a job batch's jobs, a path-job batch's sum of legs */
-    r.particles = b.rows;    /* the counters are the chain's sums */
+    /* the counters are the chain's sums; a roll-out's chain simulates the pairs its kernel counts */
+    r.particles = b.policy ? 0 : b.rows;
     r.launch = b.total > 0;  /* the chain's calls would launch nothing either */
     return r;
 }
@@ -265,7 +313,7 @@ void build_records(const Inputs& in, const Batch& b, double* seg_state, uint32_t
             r.seg_done = seg_done ? seg_done + base : nullptr;
             r.job_base = (uint32_t)base;
             if (job.n == 0) continue; /* never read: no particle maps to an empty job */
-            r.targets = job.waypoints + leg * job.num_targets * W;
+            r.targets = b.policy ? nullptr : job.waypoints + leg * job.num_targets * W;
             r.starts = leg == 0 ? job.starts : job.out_positions + (leg - 1) * job.n * W;
             r.out_q = job.out_positions + leg * job.n * W;
             r.out_collided = job.out_collided ? job.out_collided + leg * job.n : nullptr;
@@ -278,6 +326,20 @@ void build_records(const Inputs& in, const Batch& b, double* seg_state, uint32_t
     }
     h_first[b.num_jobs] = (uint32_t)base; /* == total */
     h_leg_first[b.num_jobs] = (uint32_t)rec;
+    if (b.policy) {
+        fksd::PolicyArgs p;
+        std::memset(&p, 0, sizeof(p));
+        p.keys = b.table.keys;
+        p.targets = b.table.targets;
+        p.flags = b.table.flags;
+        p.num_entries = b.table.num_entries;
+        p.terminal_distance = b.table.terminal_distance;
+        p.max_distance = b.table.max_distance;
+        p.out_choice = b.out_choice;
+        p.out_distance = b.out_distance;
+        p.out_legs_run = b.out_legs_run;
+        std::memcpy(h_records + plan_records(b).policy_record, &p, sizeof(p));
+    }
 }
 
 }  // namespace fks_batch

@@ -1,7 +1,7 @@
 /*
- * fks_batch.h — the host-side plan of a batched call (fks_forward_simulate_path, _jobs and
- * _path_jobs, on one context or sharded): one normal form for the three entries, their argument
- * checks, the controller-step segment plan and the kernel-argument records.
+ * fks_batch.h — the host-side plan of a batched call (fks_forward_simulate_path, _jobs,
+ * _path_jobs and _policy, on one context or sharded): one normal form for the four entries,
+ * their argument checks, the controller-step segment plan and the kernel-argument records.
  *
  * Nothing here calls the HIP runtime or reads an fks_context: the inputs come in a small struct,
  * device pointers are only offset and stored, never dereferenced, so the unit is built and
@@ -36,7 +36,7 @@ constexpr const char* kTargetsOneOrN = "targets must be 1 or n (SPCS:792)";
 enum Form { PATH = 0, JOBS = 1, PATH_JOBS = 2 };
 
 /* the entry a batch came through: the row of its refusals' wording (fks_batch.cpp) */
-enum Entry { ENTRY_PATH_DEVICE = 0, ENTRY_PATH_HOST, ENTRY_JOBS, ENTRY_PATH_JOBS };
+enum Entry { ENTRY_PATH_DEVICE = 0, ENTRY_PATH_HOST, ENTRY_JOBS, ENTRY_PATH_JOBS, ENTRY_POLICY_DEVICE, ENTRY_POLICY_HOST };
 
 /* what the plan reads of a context */
 struct Inputs {
@@ -76,12 +76,24 @@ struct Batch {
     /* from check_arguments: the sum of n, of num_legs, the longest job's legs, the sum of n x num_legs */
     uint64_t total = 0, legs = 0, max_legs = 0, rows = 0;
     SegmentPlan plan; /* from plan_batch */
+    /* a policy roll-out (fks_forward_simulate_policy): a path of max_legs legs whose records carry
+     * no targets, with the table and the three outputs of the selection (from_policy) */
+    bool policy = false;
+    bool has_table = false; /* the caller passed a table (a NULL one is refused) */
+    fks_policy_table table{};
+    uint32_t* out_choice = nullptr;
+    double* out_distance = nullptr;
+    uint32_t* out_legs_run = nullptr;
 
     const fks_path_job* jobs() const { return converted.empty() ? external : converted.data(); }
 };
 void from_path(Batch* b, Entry entry, const double* starts, uint64_t n, const double* waypoints, uint64_t num_legs,
                uint64_t num_targets, uint64_t first_particle_id, int32_t allow_contacts, double* out_positions,
                uint8_t* out_collided, uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags);
+void from_policy(Batch* b, Entry entry, const double* starts, uint64_t n, const fks_policy_table* table, uint64_t max_legs,
+                 uint64_t first_particle_id, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
+                 uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags, uint32_t* out_choice,
+                 double* out_distance, uint32_t* out_legs_run);
 void from_jobs(Batch* b, const fks_job* jobs, uint64_t num_jobs);
 void from_path_jobs(Batch* b, const fks_path_job* jobs, uint64_t num_jobs);
 /* a one-leg path job as the job it came from */
@@ -96,16 +108,18 @@ fks_status plan_batch(const Inputs& in, Batch* b, std::string* why);
 
 /* the records of a planned batch */
 struct RecordPlan {
-    size_t records = 0;         /* SimArgs-sized units of the upload: the records, then job_first and leg_first */
+    size_t records = 0;         /* SimArgs-sized units of the upload: the records, then job_first and leg_first,
+                                   then a roll-out's PolicyArgs */
+    size_t policy_record = 0;   /* the unit that holds a roll-out's PolicyArgs (0: not a roll-out) */
     uint64_t call_advance = 0;  /* what the call adds to the call index ... */
-    uint64_t particles = 0;     /* ... and to last.particles */
+    uint64_t particles = 0;     /* ... and to last.particles (a roll-out: 0, its kernel counts the pairs it simulates) */
     bool launch = false;        /* false: every job is empty, nothing is uploaded or launched */
 };
 RecordPlan plan_records(const Batch& b);
 /* Writes the upload into h_records (plan_records(b).records units): one record per (job, leg),
- * job-major, then job_first[num_jobs + 1] and leg_first[num_jobs + 1].  d_records is where the
- * upload will lie on the device, seg_state / seg_done the batch's arrays (null where the plan
- * needs none). */
+ * job-major, then job_first[num_jobs + 1] and leg_first[num_jobs + 1], then a roll-out's
+ * PolicyArgs (unit plan_records(b).policy_record).  d_records is where the upload will lie on the
+ * device, seg_state / seg_done the batch's arrays (null where the plan needs none). */
 void build_records(const Inputs& in, const Batch& b, double* seg_state, uint32_t* seg_done, const fksd::SimArgs* d_records,
                    fksd::SimArgs* h_records);
 

@@ -67,6 +67,13 @@ extern "C" __global__ void fks_simulate_se3_path_jobs(const fksd::SimArgs* args)
 extern "C" __global__ void fks_simulate_linked_path_jobs_small(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_se2_path_jobs_small(const fksd::SimArgs* args);
 extern "C" __global__ void fks_simulate_se3_path_jobs_small(const fksd::SimArgs* args);
+extern "C" __global__ void fks_simulate_linked_policy(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
+extern "C" __global__ void fks_simulate_linked_lean_policy(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
+extern "C" __global__ void fks_simulate_se2_policy(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
+extern "C" __global__ void fks_simulate_se3_policy(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
+extern "C" __global__ void fks_simulate_linked_policy_small(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
+extern "C" __global__ void fks_simulate_se2_policy_small(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
+extern "C" __global__ void fks_simulate_se3_policy_small(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
 extern "C" __global__ void fks_check_configs_linked(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se2(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se3(const fksd::SimArgs* args);
@@ -106,6 +113,16 @@ const sim_kernel_t kKernels[KF_COUNT][2][4] = {
 sim_kernel_t kernel_of(int form, bool small, int robot_type, bool lean = false) {
     const int family = robot_type == FKS_ROBOT_SE2 ? 2 : (robot_type == FKS_ROBOT_SE3 ? 3 : (lean ? 1 : 0));
     return kKernels[form][small ? 1 : 0][family];
+}
+/* the policy roll-out's kernels (fks_forward_simulate_policy): the path kernels' POLICY flavour,
+ * with the call's PolicyArgs as their second argument; by budget and family as above */
+typedef void (*policy_kernel_t)(const fksd::SimArgs*, const fksd::PolicyArgs*);
+const policy_kernel_t kPolicyKernels[2][4] = {
+    {fks_simulate_linked_policy, fks_simulate_linked_lean_policy, fks_simulate_se2_policy, fks_simulate_se3_policy},
+    {fks_simulate_linked_policy_small, fks_simulate_linked_policy_small, fks_simulate_se2_policy_small, fks_simulate_se3_policy_small}};
+policy_kernel_t policy_kernel_of(bool small, int robot_type, bool lean) {
+    const int family = robot_type == FKS_ROBOT_SE2 ? 2 : (robot_type == FKS_ROBOT_SE3 ? 3 : (lean ? 1 : 0));
+    return kPolicyKernels[small ? 1 : 0][family];
 }
 
 using fks_batch::splitmix64;
@@ -294,6 +311,11 @@ struct fks_context {
     unsigned long long* h_counters = nullptr; /* pinned */
     fksd::SimArgs* d_args = nullptr;          /* kernel arguments, read through a pointer */
     fksd::SimArgs* h_args = nullptr;          /* pinned staging for d_args */
+    uint32_t* d_policy_choice = nullptr; /* fks_forward_simulate_policy's host entry: the selection's staging */
+    double* d_policy_distance = nullptr;
+    uint32_t* d_policy_legs = nullptr;
+    double* d_policy_in = nullptr; /* and its inputs' own: the starts with the table behind them */
+    size_t cap_policy_sel = 0, cap_policy_in = 0;
     fksd::SimArgs* d_path_args = nullptr;     /* a batch's records (fks_batch::build_records): one per (job, leg) of
                                                  its normal form (a path's legs, a job batch's jobs), then job_first
                                                  and leg_first (SimArgs.job_first) */
@@ -745,6 +767,10 @@ void fks_destroy(fks_context* ctx) {
     if (ctx->h_args) (void)hipHostFree(ctx->h_args);
     if (ctx->d_path_args) (void)hipFree(ctx->d_path_args);
     if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
+    if (ctx->d_policy_choice) (void)hipFree(ctx->d_policy_choice);
+    if (ctx->d_policy_distance) (void)hipFree(ctx->d_policy_distance);
+    if (ctx->d_policy_legs) (void)hipFree(ctx->d_policy_legs);
+    if (ctx->d_policy_in) (void)hipFree(ctx->d_policy_in);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     delete ctx;
@@ -1289,6 +1315,8 @@ static fks_status settle(fks_context* ctx) {
     ctx->last.kernel_ms = (double)ms;
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
     ctx->last.calls = 1;
+    /* a policy roll-out's particles are the (particle, leg) pairs its kernel simulated (0 otherwise) */
+    ctx->last.particles += c[fksd::kCntPolicyPairs];
     ctx->total.particles += ctx->last.particles;
     ctx->total.controller_steps += ctx->last.controller_steps;
     ctx->total.microsteps += ctx->last.microsteps;
@@ -1400,6 +1428,7 @@ static fks_job plain_call(const double* d_starts, uint64_t n, const double* d_ta
 struct Launch {
     int32_t kind = FKS_KERNEL_NONE; /* fks_get_launch_info: last_kernel */
     sim_kernel_t kernel = nullptr;
+    policy_kernel_t policy = nullptr; /* a policy roll-out's kernel: launched with the call's PolicyArgs */
     hipFunction_t shaped = nullptr;
     ShapedModule* module = nullptr; /* of `shaped`: its launches are counted */
     bool coop = false;              /* the cooperative geometry: one workgroup per particle */
@@ -1415,6 +1444,12 @@ static Launch choose_kernel(fks_context* ctx, const SimRequest& rq, const fks_ba
         /* the robot's batched module serves all three forms through its PATH && JOBS kernel when
          * the records fit its bound; otherwise the generic kernel of the batch's own form */
         const fks_batch::Batch& b = *rq.batch;
+        if (b.policy) {
+            /* always the generic policy kernels, also when a batched shaped module exists */
+            l.kind = plan.small ? FKS_KERNEL_POLICY_SMALL_BATCH : FKS_KERNEL_POLICY;
+            l.policy = policy_kernel_of(plan.small, rt, ctx->lean);
+            return l;
+        }
         static const int32_t kGeneric[3][2] = {{FKS_KERNEL_PATH, FKS_KERNEL_PATH_SMALL_BATCH},
                                                {FKS_KERNEL_JOBS, FKS_KERNEL_JOBS_SMALL_BATCH},
                                                {FKS_KERNEL_PATH_JOBS, FKS_KERNEL_PATH_JOBS_SMALL_BATCH}};
@@ -1564,6 +1599,9 @@ static fks_status simulate_device(fks_context* ctx, const SimRequest& rq) {
         HIP_TRY(ctx, hipModuleLaunchKernel(l.shaped, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes, s, params,
                                            nullptr));
         l.module->launches++;
+    } else if (l.policy) {
+        const fksd::PolicyArgs* pol = reinterpret_cast<const fksd::PolicyArgs*>(ctx->d_path_args + records.policy_record);
+        hipLaunchKernelGGL(l.policy, dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args, pol);
     } else if (l.coop) {
         hipLaunchKernelGGL(l.kernel, dim3((uint32_t)n), dim3(64 * ctx->coop_waves), ctx->coop_lds_bytes, s, d_launch_args);
     } else {
@@ -1964,6 +2002,102 @@ static fks_status simulate_batch_host(fks_context* ctx, const fks_batch::Inputs&
         if (job.out_error_flags) std::memcpy(job.out_error_flags, h_err + oat, r * sizeof(uint32_t));
         oat += r;
     }
+    ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
+    return FKS_OK;
+}
+
+fks_status fks_forward_simulate_policy_device(fks_context* ctx, const double* d_starts, uint64_t n, const fks_policy_table* table,
+                                              uint64_t max_legs, uint64_t first_particle_id, int32_t allow_contacts,
+                                              double* d_out_positions, uint8_t* d_out_collided, uint32_t* d_out_microsteps,
+                                              uint32_t* d_out_resolver_iterations, uint32_t* d_out_error_flags,
+                                              uint32_t* d_out_choice, double* d_out_distance, uint32_t* d_out_legs_run,
+                                              void* stream, int32_t synchronize) {
+    fks_batch::Inputs in;
+    fks_batch::Batch b;
+    fks_batch::from_policy(&b, fks_batch::ENTRY_POLICY_DEVICE, d_starts, n, table, max_legs, first_particle_id, allow_contacts,
+                           d_out_positions, d_out_collided, d_out_microsteps, d_out_resolver_iterations, d_out_error_flags,
+                           d_out_choice, d_out_distance, d_out_legs_run);
+    const fks_status st = plan_entry(ctx, &in, &b);
+    if (st != FKS_OK) return st;
+    return run_batch(ctx, in, b, stream, synchronize);
+}
+
+/* The table goes up with the starts in one copy (a staging buffer of the roll-out's own, so that a
+ * large table grows nothing else: the starts, the keys, the targets, then the flags), the outputs
+ * use the path's staging buffers and three of the roll-out's own, and each array comes down in
+ * one copy */
+fks_status fks_forward_simulate_policy(fks_context* ctx, const double* starts, uint64_t n, const fks_policy_table* table,
+                                       uint64_t max_legs, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
+                                       uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags,
+                                       uint32_t* out_choice, double* out_distance, uint32_t* out_legs_run) {
+    fks_batch::Inputs in;
+    fks_batch::Batch b;
+    fks_batch::from_policy(&b, fks_batch::ENTRY_POLICY_HOST, starts, n, table, max_legs, 0, allow_contacts, out_positions,
+                           out_collided, out_microsteps, out_resolver_iterations, out_error_flags, out_choice, out_distance,
+                           out_legs_run);
+    fks_status st = plan_entry(ctx, &in, &b);
+    if (st != FKS_OK) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = settle(ctx);
+    if (st != FKS_OK) return st;
+    if (n == 0) return run_batch(ctx, in, b, nullptr, 1);
+    const size_t W = (size_t)ctx->R.W;
+    const uint64_t M = table->num_entries, rows = n * max_legs, sel = n * (max_legs + 1);
+    /* in doubles: starts, keys, targets, flags (two to a double) */
+    const uint64_t in_words = (n + 2 * M) * W + (table->flags ? (M + 1) / 2 : 0);
+    if (rows > ctx->cap_particles) {
+        HIP_TRY(ctx, ensure(&ctx->d_starts, rows * W));
+        HIP_TRY(ctx, ensure(&ctx->d_out, rows * W));
+        HIP_TRY(ctx, ensure(&ctx->d_coll, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_micro, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_res, rows));
+        HIP_TRY(ctx, ensure(&ctx->d_err, rows));
+        ctx->cap_particles = rows;
+    }
+    if (in_words > ctx->cap_policy_in) { /* a large table grows this buffer alone */
+        HIP_TRY(ctx, ensure(&ctx->d_policy_in, in_words));
+        ctx->cap_policy_in = in_words;
+    }
+    if (sel > ctx->cap_policy_sel) {
+        HIP_TRY(ctx, ensure(&ctx->d_policy_choice, sel));
+        HIP_TRY(ctx, ensure(&ctx->d_policy_distance, sel));
+        HIP_TRY(ctx, ensure(&ctx->d_policy_legs, sel)); /* >= n, whatever the next call's legs */
+        ctx->cap_policy_sel = sel;
+    }
+    ctx->jobs_stage.resize(in_words * sizeof(double));
+    double* h_in = reinterpret_cast<double*>(ctx->jobs_stage.data());
+    std::memcpy(h_in, starts, n * W * sizeof(double));
+    std::memcpy(h_in + n * W, table->keys, M * W * sizeof(double));
+    std::memcpy(h_in + (n + M) * W, table->targets, M * W * sizeof(double));
+    if (table->flags) {
+        h_in[in_words - 1] = 0.0; /* the odd entry's other half */
+        std::memcpy(h_in + (n + 2 * M) * W, table->flags, M * sizeof(uint32_t));
+    }
+    HIP_TRY(ctx, hipMemcpy(ctx->d_policy_in, h_in, in_words * sizeof(double), hipMemcpyHostToDevice));
+    fks_path_job& dev = b.converted[0]; /* the same roll-out over the staging buffers */
+    dev.starts = ctx->d_policy_in;
+    dev.out_positions = ctx->d_out;
+    dev.out_collided = ctx->d_coll;
+    dev.out_microsteps = ctx->d_micro;
+    dev.out_resolver_iterations = ctx->d_res;
+    dev.out_error_flags = ctx->d_err;
+    b.table.keys = ctx->d_policy_in + n * W;
+    b.table.targets = ctx->d_policy_in + (n + M) * W;
+    b.table.flags = table->flags ? reinterpret_cast<const uint32_t*>(ctx->d_policy_in + (n + 2 * M) * W) : nullptr;
+    b.out_choice = ctx->d_policy_choice;
+    b.out_distance = ctx->d_policy_distance;
+    b.out_legs_run = ctx->d_policy_legs;
+    st = run_batch(ctx, in, b, nullptr, 1);
+    if (st != FKS_OK) return st;
+    HIP_TRY(ctx, hipMemcpy(out_positions, ctx->d_out, rows * W * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_collided) HIP_TRY(ctx, hipMemcpy(out_collided, ctx->d_coll, rows, hipMemcpyDeviceToHost));
+    if (out_microsteps) HIP_TRY(ctx, hipMemcpy(out_microsteps, ctx->d_micro, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_resolver_iterations)
+        HIP_TRY(ctx, hipMemcpy(out_resolver_iterations, ctx->d_res, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_error_flags) HIP_TRY(ctx, hipMemcpy(out_error_flags, ctx->d_err, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out_choice, ctx->d_policy_choice, sel * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_distance) HIP_TRY(ctx, hipMemcpy(out_distance, ctx->d_policy_distance, sel * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_legs_run) HIP_TRY(ctx, hipMemcpy(out_legs_run, ctx->d_policy_legs, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
     return FKS_OK;
 }

@@ -417,6 +417,23 @@ struct SimArgs {
     uint64_t jobs_total;
 };
 
+/* The second argument of the policy kernels (fks_forward_simulate_policy, the *_policy kernels):
+ * one record per call, staged behind the legs' records.  The records are a path's, one per leg,
+ * with targets == NULL: a particle's target of leg k is targets + choice x W, chosen by
+ * policy_select at the leg's first segment and kept in out_choice[k][p] for the later ones.
+ * The table is host-written and never written by the kernel; the three outputs are [legs + 1][n],
+ * [legs + 1][n] and [n] of the record's own particles (out_distance and out_legs_run may be NULL) */
+struct PolicyArgs {
+    const double* keys;    /* [M][W] */
+    const double* targets; /* [M][W] */
+    const uint32_t* flags; /* [M] or NULL */
+    uint64_t num_entries;  /* M */
+    double terminal_distance, max_distance;
+    uint32_t* out_choice;
+    double* out_distance;
+    uint32_t* out_legs_run;
+};
+
 enum {
     kCntSuccessful = 0,
     kCntUnsuccessful,
@@ -440,6 +457,8 @@ enum {
 /* per-phase s_memtime cycle sums (lane 0 of every wave), after the counters and the
  * particle queue in the counter buffer; order = FKS_PHASE_* in fks_capi.h */
 enum {
+    /* the (particle, leg) pairs a policy call simulated, in the spare word behind the ticket counter */
+    kCntPolicyPairs = kNumCounters + 1,
     kPhaseBase = kNumCounters + 2,
     /* the running sums of the relative heavy-segment test (SimArgs.seg_heavy_rel), on a cache line
      * of their own (not the ticket counter's) */

@@ -522,7 +522,7 @@ __device__ __forceinline__ void pid_set(Sim& s, int ln, double integral, double 
     }
 }
 /* the wave's call totals in LDS (Sim::totals), flushed once when the queue is drained */
-enum { kTotSteps = 0, kTotMicro, kTotResolver, kTotLsq, kTotErrors, kWaveTotals };
+enum { kTotSteps = 0, kTotMicro, kTotResolver, kTotLsq, kTotErrors, kTotPolicyPairs, kWaveTotals };
 
 /* The lane index made opaque to the optimiser at the head of the microstep and
  * resolver loops: the per-lane LDS / workspace addresses derived from it are then
@@ -994,14 +994,16 @@ __device__ FKS_SHAPE_INLINE double control_action(Sim& s, const double* cfg, con
     return u;
 }
 
-/* configuration distance for the simulation shortcut (SPCS:898) */
+/* the robot's configuration distance (ComputeConfigurationDistanceTo) from cfg to target over the
+ * robot tables `joints` and `dofj` (linked robots): the one definition on the device, for the
+ * simulation shortcut and for a policy table's selection */
 template <int RT>
-__device__ FKS_SHAPE_INLINE double config_distance(Sim& s, const double* cfg, const double* target) {
-    const RobotDev& R = s.A->R;
+__device__ __forceinline__ double config_distance_of(const RobotDev& R, const JointDev* joints, const int32_t* dofj, const double* cfg,
+                                                     const double* target) {
     if constexpr (RT == FKS_ROBOT_LINKED) {
         double sum = 0.0;
         for (int k = 0; k < RDIM(R, D); ++k) {
-            const JointDev& jd = s.joints()[s.dofj()[k]];
+            const JointDev& jd = joints[dofj[k]];
             const double sd = (jd.type == FKS_JOINT_CONTINUOUS) ? fks_math::wrap_revolute(target[k] - cfg[k])
                                                                 : target[k] - cfg[k];
             const double d = gp(R.weights)[k] * dabs(sd);
@@ -1026,6 +1028,12 @@ __device__ FKS_SHAPE_INLINE double config_distance(Sim& s, const double* cfg, co
         const double angle = dsqrt((tw[3] * tw[3] + tw[4] * tw[4]) + tw[5] * tw[5]);
         return gp(R.weights)[0] * dsqrt((dx * dx + dy * dy) + dz * dz) + gp(R.weights)[1] * angle;
     }
+}
+
+/* configuration distance for the simulation shortcut (SPCS:898) */
+template <int RT>
+__device__ FKS_SHAPE_INLINE double config_distance(Sim& s, const double* cfg, const double* target) {
+    return config_distance_of<RT>(s.A->R, s.joints(), s.dofj(), cfg, target);
 }
 
 /* ---------------- provably-free rounds ----------------
@@ -3917,6 +3925,71 @@ __device__ __forceinline__ uint32_t job_of(const SimArgs* __restrict__ args, uin
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)(lo + c - 1u));
 }
 
+/* what ResetPosition leaves of value v of configuration word ln (SetPosition: joint limits,
+ * continuous dofs and the SE(2) angle wrapped; an SE(3) pose as it is): the one definition, for
+ * the seg == 0 branch of simulate_particles and for the selection of the configuration a
+ * roll-out's last leg returned.  reset_words is the configuration's width (a linked robot's D). */
+template <int RT>
+__device__ __forceinline__ int reset_words(int D) {
+    return RT == FKS_ROBOT_LINKED ? D : (RT == FKS_ROBOT_SE2 ? 3 : 12);
+}
+template <int RT>
+__device__ __forceinline__ double reset_word(const SimArgs& A, const double* shared, int ln, double v) {
+    if constexpr (RT == FKS_ROBOT_LINKED) {
+        const JointDev& jd = reinterpret_cast<const JointDev*>(shared + LAY(A).joints)[reinterpret_cast<const int32_t*>(shared + LAY(A).dofj)[ln]];
+        return (jd.type == FKS_JOINT_CONTINUOUS) ? fks_math::wrap_revolute(v) : clamp(v, jd.lo, jd.hi);
+    } else if constexpr (RT == FKS_ROBOT_SE2) {
+        return (ln == 2) ? fks_math::wrap_revolute(v) : v;
+    } else {
+        return v;
+    }
+}
+
+/* The selection of a policy table (fks_policy_table in fks_capi.h; the host twin is
+ * fks_policy_select): the verdict for the reset configuration p (W doubles in LDS) and, in *out_d,
+ * the chosen entry's distance.  Wave-wide and wave-uniform.  Lanes take entries ln, ln + 64, ...
+ * and keep their own (d, i) under the strict < from +inf, so a lane holds its lowest index of
+ * its smallest distance and a NaN never wins; the butterfly then reduces the pair by (smaller d,
+ * then smaller i), which is the ascending scan's result whatever the lane count.  The distance
+ * is config_distance_of<RT> with cfg = p and target = the key, evaluated per lane.
+ * Cold code (once per leg): out of line, so nothing of it is live in the step loop. */
+template <int RT>
+__device__ __noinline__ uint32_t policy_select(const SimArgs* __restrict__ Ap, const PolicyArgs* __restrict__ P, const double* shared,
+                                               const double* p, int ln, double* out_d) {
+    const SimArgs& A = *Ap;
+    const RobotDev& R = A.R;
+    const int W = RDIM(R, W);
+    const uint64_t M = P->num_entries;
+    double best = __builtin_inf();
+    uint32_t choice = FKS_POLICY_NONE;
+    const JointDev* joints = reinterpret_cast<const JointDev*>(shared + LAY(A).joints);
+    const int32_t* dofj = reinterpret_cast<const int32_t*>(shared + LAY(A).dofj);
+    for (uint64_t i = (uint64_t)ln; i < M; i += (uint64_t)kWave) {
+        const double d = config_distance_of<RT>(R, joints, dofj, p, P->keys + i * (uint64_t)W);
+        if (d < best) {
+            best = d;
+            choice = (uint32_t)i;
+        }
+    }
+    /* every lane ends with the wave's pair; a lane without an entry holds (+inf, NONE) */
+#pragma unroll
+    for (int m = 1; m < kWave; m <<= 1) {
+        const double od = __shfl_xor(best, m, kWave);
+        const uint32_t oi = (uint32_t)__shfl_xor((int)choice, m, kWave);
+        if (od < best || (od == best && oi < choice)) {
+            best = od;
+            choice = oi;
+        }
+    }
+    choice = (uint32_t)__builtin_amdgcn_readfirstlane((int)choice);
+    best = readfirstlane_f64(best);
+    *out_d = best;
+    /* the lost test comes first; arrived is strict (SPCS:899) */
+    if (choice == FKS_POLICY_NONE || best > P->max_distance) return FKS_POLICY_LOST;
+    if (P->flags && (P->flags[choice] & FKS_POLICY_ENTRY_TERMINAL) && best < P->terminal_distance) return choice | FKS_POLICY_ARRIVED;
+    return choice;
+}
+
 /* PATH: the waypoint-path kernels (fks_forward_simulate_path).  args is then an array of
  * A.path_legs records, one per leg (SimArgs.path_legs), and a particle's ticket space is
  * path_legs x nseg segments: a leg boundary is one more segment boundary, at which the
@@ -3928,9 +4001,20 @@ __device__ __forceinline__ uint32_t job_of(const SimArgs* __restrict__ args, uin
  * PATH && JOBS: the path-job kernels (fks_forward_simulate_path_jobs).  args is job-major, one
  * record per (job, leg): leg k of job j is record leg_first[j] + k, with leg_first[num_jobs + 1]
  * stored behind job_first.  The ticket space is one path's over all jobs' particles, as long
- * as the longest job's (SimArgs.path_legs_max); a record's path_legs is its own job's */
-template <int RT, bool TR, bool IND = false, bool LEAN = false, int COOP = 0, bool PATH = false, bool JOBS = false>
-__device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ args, double* lds_mem) {
+ * as the longest job's (SimArgs.path_legs_max); a record's path_legs is its own job's
+ * POLICY (with PATH && !JOBS only): the policy kernels (fks_forward_simulate_policy).  The records
+ * are a path's without targets; pol is the call's PolicyArgs.  At seg == 0 of every leg the reset
+ * configuration selects its entry (policy_select): the entry's target is the leg's, or the
+ * particle stops there (lost or arrived), fills the rows it does not run and retires its ticket
+ * space (seg_done = path_legs x nseg, so every later ticket of it is stale).  A later segment of
+ * the leg reads the choice back from out_choice[leg][p] (device-coherent, published with the
+ * resting state by the fences around seg_done).  The particle's end of its last leg selects once
+ * more (row path_legs of out_choice / out_distance) */
+template <int RT, bool TR, bool IND = false, bool LEAN = false, int COOP = 0, bool PATH = false, bool JOBS = false,
+          bool POLICY = false>
+__device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ args, double* lds_mem,
+                                                   const PolicyArgs* __restrict__ pol = nullptr) {
+    static_assert(!POLICY || (PATH && !JOBS && !TR && !IND && COOP == 0), "POLICY is a flavour of the plain path kernels");
     const SimArgs& A = *args;
     /* particles in the ticket space: the call's, or all jobs' (equal in every record) */
     auto batch_n = [&]() -> uint64_t {
@@ -4061,6 +4145,9 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
                     if (wt[kTotLsq]) atomicAdd(A.counters + kCntLsqRows, (unsigned long long)wt[kTotLsq]);
                     if (bytes) atomicAdd(A.counters + kCntSdfBytes, (unsigned long long)bytes);
                     if (wt[kTotErrors]) atomicAdd(A.counters + kCntErrorParticles, (unsigned long long)wt[kTotErrors]);
+                    if constexpr (POLICY) {
+                        if (wt[kTotPolicyPairs]) atomicAdd(A.counters + kCntPolicyPairs, (unsigned long long)wt[kTotPolicyPairs]);
+                    }
                     const uint64_t* sc = self_counters(s);
                     if (sc[0]) atomicAdd(A.counters + kCntSelfChecks, (unsigned long long)sc[0]);
                     if (sc[1]) atomicAdd(A.counters + kCntSelfPoints, (unsigned long long)sc[1]);
@@ -4137,7 +4224,7 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             }
             return start[i];
         };
-        const double* target = (A.num_targets == A.n) ? A.targets + local * (uint64_t)W : A.targets;
+        const double* target = (A.num_targets == A.n) ? A.targets + local * (uint64_t)W : A.targets; /* POLICY: below */
         bool collided = false;
         bool any_failed = false;
         if (seg == 0) {
@@ -4147,17 +4234,7 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
                 pid_set<RT>(s, ln, A.pid_io ? A.pid_io[local * 2ull * (uint64_t)D + ln] : 0.0,
                             A.pid_io ? A.pid_io[local * 2ull * (uint64_t)D + D + ln] : 0.0);
             /* ResetPosition(start): SetPosition enforces joint limits / angle wrap */
-            if constexpr (RT == FKS_ROBOT_LINKED) {
-                if (ln < D) {
-                    const JointDev& jd = s.joints()[s.dofj()[ln]];
-                    cfg[ln] = (jd.type == FKS_JOINT_CONTINUOUS) ? fks_math::wrap_revolute(start_at(ln))
-                                                                : clamp(start_at(ln), jd.lo, jd.hi);
-                }
-            } else if constexpr (RT == FKS_ROBOT_SE2) {
-                if (ln < 3) cfg[ln] = (ln == 2) ? fks_math::wrap_revolute(start_at(2)) : start_at(ln);
-            } else {
-                if (ln < 12) cfg[ln] = start_at(ln);
-            }
+            if (ln < reset_words<RT>(D)) cfg[ln] = reset_word<RT>(A, s.shared(), ln, start_at(ln));
             if constexpr (PATH) {
                 /* the chain's next call would start without round proofs of the call before */
                 if (leg > 0 && ln < RDIM(R, nrounds)) s.rstate[kRoundState * ln + 12] = kInvalidRound;
@@ -4177,6 +4254,49 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             for (int e = ln; e < nrc; e += kWave) s.rstate[e] = load_coherent(st + 2 * D + 4 + e);
         }
         wsync();
+        if constexpr (POLICY) {
+            /* the leg's target: chosen here at its first segment, read back at a later one */
+            uint32_t* choice_row = pol->out_choice + (uint64_t)leg * A.n + local;
+            uint32_t choice;
+            if (seg == 0) {
+                double d;
+                choice = policy_select<RT>(&A, pol, s.shared(), cfg, ln, &d);
+                if (ln == 0) {
+                    __hip_atomic_store(choice_row, choice, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (pol->out_distance) pol->out_distance[(uint64_t)leg * A.n + local] = d;
+                }
+                if (choice >= FKS_POLICY_ARRIVED) {
+                    /* lost or arrived: the particle stops before this leg.  The rows it does not
+                     * run: the configuration handed over (its bytes, not reset) in every further
+                     * position row, zeros in the other four, NONE / +inf in the selections after
+                     * this one; nothing is counted */
+                    const uint32_t rest = A.path_legs - leg;
+                    const double q = (ln < W) ? start_at(ln) : 0.0;
+                    for (uint32_t r = 0; r < rest; ++r)
+                        if (ln < W) A.out_q[((uint64_t)r * A.n + local) * (uint64_t)W + ln] = q;
+                    for (uint32_t r = (uint32_t)ln; r < rest; r += (uint32_t)kWave) {
+                        const uint64_t at = (uint64_t)r * A.n + local;
+                        if (A.out_collided) A.out_collided[at] = 0;
+                        if (A.out_micro) A.out_micro[at] = 0;
+                        if (A.out_resolver) A.out_resolver[at] = 0;
+                        if (A.out_err) A.out_err[at] = 0;
+                        choice_row[(uint64_t)(r + 1u) * A.n] = FKS_POLICY_NONE;
+                        if (pol->out_distance) pol->out_distance[(uint64_t)(leg + r + 1u) * A.n + local] = __builtin_inf();
+                    }
+                    if (ln == 0) {
+                        if (pol->out_legs_run) pol->out_legs_run[local] = leg;
+                        if (nsegs > 1) __hip_atomic_store(A.seg_done + local, nsegs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        s.phase()[FKS_PHASE_PARTICLE] += __builtin_amdgcn_s_memtime();
+                    }
+                    wsync();
+                    continue; /* the wave takes its next ticket: no carry, and no wave waits for this one */
+                }
+                if (ln == 0) s.totals()[kTotPolicyPairs]++; /* flushed with the wave's other sums */
+            } else {
+                choice = __hip_atomic_load(choice_row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            target = pol->targets + (uint64_t)__builtin_amdgcn_readfirstlane((int)choice) * (uint64_t)W;
+        }
         double* Tcur = s.lds() + LAY(*s.A).Tcur;
         double* Tprev = s.lds() + LAY(*s.A).Tprev;
         bool ended = false;
@@ -4281,6 +4401,22 @@ __device__ __forceinline__ void simulate_particles(const SimArgs* __restrict__ a
             const uint64_t t_end = __builtin_amdgcn_s_memtime();
             s.phase()[FKS_PHASE_OUTPUT] += t_end - t_out;
             s.phase()[FKS_PHASE_PARTICLE] += t_end;
+        }
+        if constexpr (POLICY) {
+            /* the particle ran every leg: the selection of where it ended (row path_legs) */
+            if (ended && leg + 1u == A.path_legs) {
+                double* p = s.lds() + LAY(*s.A).tgt;
+                wsync();
+                if (ln < W) p[ln] = reset_word<RT>(A, s.shared(), ln, cfg[ln]);
+                wsync();
+                double d;
+                const uint32_t choice = policy_select<RT>(&A, pol, s.shared(), p, ln, &d);
+                if (ln == 0) {
+                    pol->out_choice[(uint64_t)A.path_legs * A.n + local] = choice;
+                    if (pol->out_distance) pol->out_distance[(uint64_t)A.path_legs * A.n + local] = d;
+                    if (pol->out_legs_run) pol->out_legs_run[local] = A.path_legs;
+                }
+            }
         }
         if (nsegs > 1) {
             /* the particle's next segment in seg_done's count: the next of this leg, or the
@@ -4600,6 +4736,46 @@ extern "C" __global__ void FKS_KERNEL_ATTRS fks_kinematics_se2(const SimArgs* __
 extern "C" __global__ void FKS_KERNEL_ATTRS fks_kinematics_se3(const SimArgs* __restrict__ args) {
     extern __shared__ __attribute__((aligned(16))) double lds_mem[];
     kinematics<FKS_ROBOT_SE3>(args, lds_mem);
+}
+
+/* policy roll-outs (fks_forward_simulate_policy): POLICY instantiations of the path kernels at the
+ * throughput budget; the second argument is the call's PolicyArgs ... */
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_policy(const SimArgs* __restrict__ args,
+                                                                        const PolicyArgs* __restrict__ pol) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true, false, true>(args, lds_mem, pol);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_policy(const SimArgs* __restrict__ args,
+                                                                             const PolicyArgs* __restrict__ pol) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, true, 0, true, false, true>(args, lds_mem, pol);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_policy(const SimArgs* __restrict__ args,
+                                                                     const PolicyArgs* __restrict__ pol) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true, false, true>(args, lds_mem, pol);
+}
+extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_policy(const SimArgs* __restrict__ args,
+                                                                     const PolicyArgs* __restrict__ pol) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true, false, true>(args, lds_mem, pol);
+}
+/* ... and at the small-batch budget, for roll-outs whose batch fits its resident waves: the wave
+ * carries its particle through every leg until it stops */
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_linked_policy_small(const SimArgs* __restrict__ args,
+                                                                                    const PolicyArgs* __restrict__ pol) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true, false, true>(args, lds_mem, pol);
+}
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_policy_small(const SimArgs* __restrict__ args,
+                                                                                 const PolicyArgs* __restrict__ pol) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true, false, true>(args, lds_mem, pol);
+}
+extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_policy_small(const SimArgs* __restrict__ args,
+                                                                                 const PolicyArgs* __restrict__ pol) {
+    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
+    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true, false, true>(args, lds_mem, pol);
 }
 
 #endif /* FKS_SHAPE_L */

@@ -294,6 +294,37 @@ class HipParticleContactSimulator:
         return {"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
                 "error_flags": errors}
 
+    def forward_simulate_policy_arrays(self, robot: RobotDescription, start_positions, table: "PolicyTable", max_legs: int,
+                                       allow_contacts: bool) -> dict:
+        """A batch rolled out under a policy table in one launch (fks_forward_simulate_policy): starts
+        (n, W), K = max_legs.  Before every leg each particle selects the table entry nearest to where
+        it is (policy_select); the entry's target is its next leg's, or it stops there (lost or
+        arrived).  Returns the five [K, n, ...] arrays of a path plus "choice" uint32 [K + 1, n],
+        "distance" [K + 1, n] and "legs_run" [n]; rows a particle does not run are defined
+        (include/fks_capi.h).  The call index advances by K."""
+        self.set_robot(robot)
+        W = robot.config_width
+        starts = np.ascontiguousarray(np.asarray(start_positions, dtype=np.float64).reshape(-1, W))
+        n, K = starts.shape[0], int(max_legs)
+        ctable, keep = table.to_c(W)
+        out = np.zeros((K, n, W), dtype=np.float64)
+        collided = np.zeros((K, n), dtype=np.uint8)
+        micro = np.zeros((K, n), dtype=np.uint32)
+        resolver = np.zeros((K, n), dtype=np.uint32)
+        errors = np.zeros((K, n), dtype=np.uint32)
+        choice = np.zeros((K + 1, n), dtype=np.uint32)
+        distance = np.zeros((K + 1, n), dtype=np.float64)
+        legs_run = np.zeros(n, dtype=np.uint32)
+        st = self._lib.fks_forward_simulate_policy(
+            self._ctx, _capi.as_ptr(starts, ctypes.c_double), n, ctypes.byref(ctable), K, 1 if allow_contacts else 0,
+            _capi.as_ptr(out, ctypes.c_double), _capi.as_ptr(collided, ctypes.c_uint8), _capi.as_ptr(micro, ctypes.c_uint32),
+            _capi.as_ptr(resolver, ctypes.c_uint32), _capi.as_ptr(errors, ctypes.c_uint32), _capi.as_ptr(choice, ctypes.c_uint32),
+            _capi.as_ptr(distance, ctypes.c_double), _capi.as_ptr(legs_run, ctypes.c_uint32))
+        del keep
+        _capi.check(st, self._ctx, "fks_forward_simulate_policy")
+        return {"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
+                "error_flags": errors, "choice": choice, "distance": distance, "legs_run": legs_run}
+
     def forward_simulate_jobs_arrays(self, robot: RobotDescription, jobs) -> list:
         """Many independent calls in one launch (fks_forward_simulate_jobs).  jobs: a sequence of
         (starts (n, W), targets (1 or n, W), allow_contacts).  Returns a list of the dicts
@@ -575,6 +606,28 @@ class HipParticleContactSimulator:
             ctypes.c_void_p(d_out_microsteps or None), ctypes.c_void_p(d_out_resolver_iterations or None),
             ctypes.c_void_p(d_out_error_flags or None), ctypes.c_void_p(stream or None), 1 if synchronize else 0)
         _capi.check(st, self._ctx, "fks_forward_simulate_path_device")
+
+    def forward_simulate_policy_device(self, robot: RobotDescription, d_starts, n: int, d_keys, d_targets, d_flags, num_entries: int,
+                                       terminal_distance: float, max_distance: float, max_legs: int, first_particle_id: int,
+                                       allow_contacts: bool, d_out_positions, d_out_choice, d_out_distance=0, d_out_legs_run=0,
+                                       d_out_collided=0, d_out_microsteps=0, d_out_resolver_iterations=0, d_out_error_flags=0,
+                                       stream=0, synchronize=False):
+        """fks_forward_simulate_policy_device: device pointers (int) as in forward_simulate_device, the
+        table's three included (d_flags may be 0); the five simulation outputs leg-major
+        ([max_legs][n]...), d_out_choice uint32 and d_out_distance double [max_legs + 1][n],
+        d_out_legs_run uint32 [n]."""
+        self.set_robot(robot)
+        table = _capi.PolicyTable(d_keys or None, d_targets or None, d_flags or None, int(num_entries), float(terminal_distance),
+                                  float(max_distance))
+        st = self._lib.fks_forward_simulate_policy_device(
+            self._ctx, ctypes.c_void_p(d_starts or None), n, ctypes.byref(table), int(max_legs), first_particle_id,
+            1 if allow_contacts else 0, ctypes.c_void_p(d_out_positions or None), ctypes.c_void_p(d_out_collided or None),
+            ctypes.c_void_p(d_out_microsteps or None), ctypes.c_void_p(d_out_resolver_iterations or None),
+            ctypes.c_void_p(d_out_error_flags or None), ctypes.c_void_p(d_out_choice or None),
+            ctypes.c_void_p(d_out_distance or None), ctypes.c_void_p(d_out_legs_run or None), ctypes.c_void_p(stream or None),
+            1 if synchronize else 0)
+        _capi.check(st, self._ctx, "fks_forward_simulate_policy_device")
+
     def forward_simulate_jobs_device(self, robot: RobotDescription, jobs, stream=0, synchronize=False):
         """fks_forward_simulate_jobs_device: jobs is a sequence of dicts with the fields of fks_job
         (d_starts, n, d_targets, num_targets, allow_contacts, d_out_positions and optionally
@@ -609,6 +662,52 @@ class HipParticleContactSimulator:
         st = self._lib.fks_forward_simulate_path_jobs_device(self._ctx, array, len(jobs), ctypes.c_void_p(stream or None),
                                                              1 if synchronize else 0)
         _capi.check(st, self._ctx, "fks_forward_simulate_path_jobs_device")
+
+
+@dataclass
+class PolicyTable:
+    """fks_policy_table over host arrays: keys and targets (M, W), terminal (M,) booleans or None,
+    and the two distances of the verdict (include/fks_capi.h)."""
+    keys: np.ndarray
+    targets: np.ndarray
+    terminal: Optional[np.ndarray] = None
+    terminal_distance: float = 0.0
+    max_distance: float = float("inf")
+
+    def to_c(self, W: int):
+        """(fks_policy_table, the arrays its pointers refer to)."""
+        keys = np.ascontiguousarray(np.asarray(self.keys, dtype=np.float64).reshape(-1, W))
+        targets = np.ascontiguousarray(np.asarray(self.targets, dtype=np.float64).reshape(-1, W))
+        if keys.shape != targets.shape:
+            raise ValueError("a policy table's keys and targets must hold the same number of configurations")
+        flags = None
+        if self.terminal is not None:
+            flags = np.ascontiguousarray(np.where(np.asarray(self.terminal).reshape(-1), _capi.POLICY_ENTRY_TERMINAL, 0),
+                                         dtype=np.uint32)
+            if flags.shape[0] != keys.shape[0]:
+                raise ValueError("a policy table's terminal flags must hold one entry per key")
+        table = _capi.PolicyTable(keys.ctypes.data if keys.size else None, targets.ctypes.data if targets.size else None,
+                                  flags.ctypes.data if flags is not None and flags.size else None, keys.shape[0],
+                                  float(self.terminal_distance), float(self.max_distance))
+        return table, (keys, targets, flags)
+
+
+def policy_select(robot: RobotDescription, table: PolicyTable, configs) -> dict:
+    """fks_policy_select: the selection of a policy table for configs (n, W) on the host, with the
+    kernels' arithmetic and without a context.  Returns "choice" uint32 [n] (an entry's index,
+    alone or or-ed with POLICY_ARRIVED, or POLICY_LOST) and "distance" [n]."""
+    W = robot.config_width
+    q = np.ascontiguousarray(np.asarray(configs, dtype=np.float64).reshape(-1, W))
+    n = q.shape[0]
+    desc, keep = robot.to_c()
+    ctable, keep_table = table.to_c(W)
+    choice = np.zeros(n, dtype=np.uint32)
+    distance = np.zeros(n, dtype=np.float64)
+    st = _capi.lib().fks_policy_select(ctypes.byref(desc), ctypes.byref(ctable), _capi.as_ptr(q, ctypes.c_double), n,
+                                       _capi.as_ptr(choice, ctypes.c_uint32), _capi.as_ptr(distance, ctypes.c_double))
+    del keep, keep_table
+    _capi.check(st, None, "fks_policy_select")
+    return {"choice": choice, "distance": distance}
 
 
 def _host_jobs(jobs, W: int):

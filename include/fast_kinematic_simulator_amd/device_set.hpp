@@ -174,6 +174,20 @@ class DeviceSet {
               ctx_, what);
     }
 
+    /* a batch rolled out under a policy table in one launch (fks_forward_simulate_policy, host
+     * buffers, its arguments): on devices[0] alone, whatever the batch's size (there is no
+     * fks_multi_* roll-out) */
+    void simulate_policy(const double* starts, uint64_t n, const fks_policy_table& table, uint64_t max_legs, bool allow_contacts,
+                         double* out_positions, uint8_t* out_collided, uint32_t* out_microsteps, uint32_t* out_resolver_iterations,
+                         uint32_t* out_error_flags, uint32_t* out_choice, double* out_distance, uint32_t* out_legs_run,
+                         const char* what) {
+        last_devices_ = 1;
+        Check(fks_forward_simulate_policy(ctx_, starts, n, &table, max_legs, allow_contacts ? 1 : 0, out_positions, out_collided,
+                                          out_microsteps, out_resolver_iterations, out_error_flags, out_choice, out_distance,
+                                          out_legs_run),
+              ctx_, what);
+    }
+
     /* many independent calls in one launch per device (fks_forward_simulate_jobs, host
      * buffers); the devices are chosen from the jobs' particles together as for simulate() */
     void simulate_jobs(const fks_job* jobs, uint64_t num_jobs, const char* what) {

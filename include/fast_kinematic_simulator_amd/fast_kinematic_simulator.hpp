@@ -288,6 +288,81 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
         }
         return out;
     }
+    /* Not part of SimulatorInterface: the batch rolled out under a policy table in one launch
+     * (fks_forward_simulate_policy), for the planner's SimulateExectionPolicy loop and its
+     * num_policy_simulations roll-outs: after every ForwardSimulateRobot the policy looks at
+     * where the particle ended, picks the nearest state, and that state's action is the next
+     * target.  State i stands for keys[i] and its action is targets[i]; terminal[i] (empty: none)
+     * marks a goal state.  results[k][i] is leg k of particle i as a path's (a leg the particle
+     * did not run holds the configuration it stopped at); choices and distances hold the
+     * selection before each leg and after the last (fks_policy_select's verdicts), legs_run the
+     * legs each particle ran.  Bit for bit what the sequence of selections and plain calls
+     * returns; runs on devices[0]. */
+    struct PolicyTable {
+        std::vector<Configuration, ConfigAlloc> keys;
+        std::vector<Configuration, ConfigAlloc> targets;
+        std::vector<bool> terminal;
+        double terminal_distance = 0.0;
+        double max_distance = std::numeric_limits<double>::infinity();
+    };
+    struct PolicyRollout {
+        std::vector<std::vector<SimulationResult>> results;
+        std::vector<std::vector<uint32_t>> choices;
+        std::vector<std::vector<double>> distances;
+        std::vector<uint32_t> legs_run;
+    };
+    PolicyRollout ForwardSimulateRobotsUnderPolicy(const std::shared_ptr<BaseRobotType>& immutable_robot,
+                                                   const std::vector<Configuration, ConfigAlloc>& start_positions,
+                                                   const PolicyTable& policy, const size_t max_legs, const bool allow_contacts) {
+        if (max_legs == 0) throw std::invalid_argument("a roll-out needs at least one leg");
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        SetRobot(robot);
+        const fks::PolicyTable plain = FlatPolicy(robot, policy);
+        const size_t K = max_legs, n = start_positions.size(), W = (size_t)robot.HipDescription().ConfigurationWidth();
+        const fks::FlatPolicyTable flat(plain, W);
+        std::vector<double> s;
+        for (const auto& c : start_positions) {
+            const std::vector<double> f = robot.ToFlat(c);
+            s.insert(s.end(), f.begin(), f.end());
+        }
+        std::vector<double> q(K * n * W), dist((K + 1) * n);
+        std::vector<uint8_t> collided(K * n);
+        std::vector<uint32_t> choice((K + 1) * n), legs(n);
+        last_micro_.assign(K * n, 0);
+        last_resolver_.assign(K * n, 0);
+        last_errors_.assign(K * n, 0);
+        dev_->simulate_policy(s.data(), n, flat.table, K, allow_contacts, q.data(), collided.data(), last_micro_.data(),
+                              last_resolver_.data(), last_errors_.data(), choice.data(), dist.data(), legs.data(),
+                              "ForwardSimulateRobotsUnderPolicy");
+        PolicyRollout out;
+        out.results.resize(K);
+        out.choices.assign(K + 1, std::vector<uint32_t>(n));
+        out.distances.assign(K + 1, std::vector<double>(n));
+        out.legs_run = legs;
+        for (size_t k = 0; k <= K; ++k)
+            for (size_t i = 0; i < n; ++i) {
+                out.choices[k][i] = choice[k * n + i];
+                out.distances[k][i] = dist[k * n + i];
+            }
+        for (size_t k = 0; k < K; ++k) {
+            out.results[k].reserve(n);
+            for (size_t i = 0; i < n; ++i) {
+                const Configuration reached = robot.FromFlat(q.data() + (k * n + i) * W);
+                out.results[k].emplace_back(reached, k < legs[i] ? policy.targets[choice[k * n + i] & ~FKS_POLICY_ARRIVED] : reached,
+                                            collided[k * n + i] != 0, true);
+            }
+        }
+        return out;
+    }
+    /* fks_policy_select on the host, without a simulator: the planner's single query during real
+     * execution (QueryBestAction), the same arithmetic as the roll-out's selections */
+    static fks::PolicySelection PolicySelect(const std::shared_ptr<BaseRobotType>& immutable_robot, const PolicyTable& policy,
+                                             const std::vector<Configuration, ConfigAlloc>& configs) {
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        std::vector<fks::Configuration> flat;
+        for (const auto& c : configs) flat.push_back(robot.ToFlat(c));
+        return fks::HipParticleContactSimulator::PolicySelect(robot.HipDescription(), FlatPolicy(robot, policy), flat);
+    }
     /* Not part of SimulatorInterface: many independent calls in one launch
      * (fks_forward_simulate_jobs), for the planner's stream of small ForwardSimulateRobots /
      * ReverseSimulateRobots calls (their semantics are the same, SPCS:838-841).  A job is one
@@ -620,6 +695,16 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
     static const DerivedRobotType& Derived(const std::shared_ptr<BaseRobotType>& robot) {
         if (!robot) throw std::invalid_argument("null robot");
         return *static_cast<const DerivedRobotType*>(robot.get()); /* SPCS:868 */
+    }
+    /* a planner-side policy table over the robot's flat configurations */
+    static fks::PolicyTable FlatPolicy(const DerivedRobotType& robot, const PolicyTable& policy) {
+        fks::PolicyTable plain;
+        for (const auto& c : policy.keys) plain.keys.push_back(robot.ToFlat(c));
+        for (const auto& c : policy.targets) plain.targets.push_back(robot.ToFlat(c));
+        plain.terminal = policy.terminal;
+        plain.terminal_distance = policy.terminal_distance;
+        plain.max_distance = policy.max_distance;
+        return plain;
     }
     static fks_planner_types::Point Point(const double* p) {
         fks_planner_types::Point o;

@@ -75,6 +75,64 @@ struct SimulationPathJob {
     bool allow_contacts = false;
 };
 
+/* A policy table (fks_policy_table): the planner's execution policy as a roll-out reads it.  State
+ * i stands for the configuration keys[i] and its action is to move to targets[i]; terminal[i]
+ * (empty: none) marks a goal state.  A particle whose nearest state is terminal and nearer than
+ * terminal_distance has arrived; one farther than max_distance from every state is lost. */
+struct PolicyTable {
+    std::vector<Configuration> keys;
+    std::vector<Configuration> targets;
+    std::vector<bool> terminal;
+    double terminal_distance = 0.0;
+    double max_distance = std::numeric_limits<double>::infinity();
+};
+/* fks_policy_select for a batch of configurations: the verdicts (an entry's index, alone or with
+ * FKS_POLICY_ARRIVED, or FKS_POLICY_LOST) and the chosen entries' distances */
+struct PolicySelection {
+    std::vector<uint32_t> choices;
+    std::vector<double> distances;
+};
+/* What ForwardSimulateRobotsUnderPolicy returns: results[leg][particle] as a path's (a leg a
+ * particle did not run holds the configuration it stopped at and no contact; target_config is
+ * the chosen entry's action, or the configuration itself for such a leg), choices and distances
+ * [leg 0 .. max_legs][particle] and legs_run[particle] (fks_forward_simulate_policy) */
+struct PolicyRollout {
+    std::vector<std::vector<SimulationResult>> results;
+    std::vector<std::vector<uint32_t>> choices;
+    std::vector<std::vector<double>> distances;
+    std::vector<uint32_t> legs_run;
+};
+/* a PolicyTable over flat configurations of width W as the C-ABI takes it; the vectors own what
+ * `table` points to */
+struct FlatPolicyTable {
+    std::vector<double> keys, targets;
+    std::vector<uint32_t> flags;
+    fks_policy_table table;
+    FlatPolicyTable(const PolicyTable& policy, size_t W) {
+        if (policy.keys.size() != policy.targets.size()) throw std::invalid_argument("a policy table needs one target per key");
+        if (!policy.terminal.empty() && policy.terminal.size() != policy.keys.size())
+            throw std::invalid_argument("a policy table's terminal flags must hold one entry per key");
+        const size_t M = policy.keys.size();
+        keys.resize(M * W);
+        targets.resize(M * W);
+        for (size_t i = 0; i < M; ++i) {
+            if (policy.keys[i].size() != W || policy.targets[i].size() != W)
+                throw std::invalid_argument("policy configuration has the wrong width");
+            std::copy(policy.keys[i].begin(), policy.keys[i].end(), keys.begin() + i * W);
+            std::copy(policy.targets[i].begin(), policy.targets[i].end(), targets.begin() + i * W);
+        }
+        for (size_t i = 0; i < policy.terminal.size(); ++i) flags.push_back(policy.terminal[i] ? FKS_POLICY_ENTRY_TERMINAL : 0u);
+        table.keys = keys.data();
+        table.targets = targets.data();
+        table.flags = flags.empty() ? nullptr : flags.data();
+        table.num_entries = M;
+        table.terminal_distance = policy.terminal_distance;
+        table.max_distance = policy.max_distance;
+    }
+    FlatPolicyTable(const FlatPolicyTable&) = delete;
+    FlatPolicyTable& operator=(const FlatPolicyTable&) = delete;
+};
+
 /* simple_simulator_interface::ForwardSimulationStepTrace as filled at SPCS:1583-1595,
  * 1615-1618, 1701-1704, 1712-1715, 1776-1779.  `kinds` tags each configuration
  * with the FKS_TRACE_* push site it came from. */
@@ -421,6 +479,72 @@ class HipParticleContactSimulator {
                 r.error_flags = errors[row];
             }
         return results;
+    }
+    /* The batch rolled out under a policy table in one launch (fks_forward_simulate_policy; the
+     * planner's SimulateExectionPolicy loop: after every ForwardSimulateRobot the policy looks at
+     * where the particle ended, picks the nearest state, and that state's action is the next
+     * target).  Before each of at most max_legs legs every particle selects its entry
+     * (PolicySelect); a lost or arrived particle stops.  Bit for bit what that sequence of plain
+     * calls returns; a particle starts its next leg when its own leg ends. */
+    PolicyRollout ForwardSimulateRobotsUnderPolicy(const RobotDescription& immutable_robot,
+                                                   const std::vector<Configuration>& start_positions, const PolicyTable& policy,
+                                                   size_t max_legs, bool allow_contacts) {
+        if (max_legs == 0) throw std::invalid_argument("a roll-out needs at least one leg");
+        SetRobot(immutable_robot);
+        const size_t W = (size_t)immutable_robot.ConfigurationWidth(), K = max_legs, n = start_positions.size();
+        const FlatPolicyTable flat(policy, W);
+        std::vector<double> s(n * W), out(K * n * W), dist((K + 1) * n);
+        for (size_t i = 0; i < n; ++i) {
+            if (start_positions[i].size() != W) throw std::invalid_argument("start configuration has the wrong width");
+            std::copy(start_positions[i].begin(), start_positions[i].end(), s.begin() + i * W);
+        }
+        std::vector<uint8_t> collided(K * n);
+        std::vector<uint32_t> micro(K * n), resolver(K * n), errors(K * n), choice((K + 1) * n), legs(n);
+        dev_.simulate_policy(s.data(), n, flat.table, K, allow_contacts, out.data(), collided.data(), micro.data(), resolver.data(),
+                             errors.data(), choice.data(), dist.data(), legs.data(), "ForwardSimulateRobotsUnderPolicy");
+        PolicyRollout r;
+        r.results.assign(K, std::vector<SimulationResult>(n));
+        r.choices.assign(K + 1, std::vector<uint32_t>(n));
+        r.distances.assign(K + 1, std::vector<double>(n));
+        r.legs_run = legs;
+        for (size_t k = 0; k <= K; ++k)
+            for (size_t i = 0; i < n; ++i) {
+                r.choices[k][i] = choice[k * n + i];
+                r.distances[k][i] = dist[k * n + i];
+            }
+        for (size_t k = 0; k < K; ++k)
+            for (size_t i = 0; i < n; ++i) {
+                SimulationResult& res = r.results[k][i];
+                const size_t row = k * n + i;
+                res.result_config.assign(out.begin() + row * W, out.begin() + (row + 1) * W);
+                res.target_config = k < legs[i] ? policy.targets[choice[row] & ~FKS_POLICY_ARRIVED] : res.result_config;
+                res.did_contact = collided[row] != 0;
+                res.outcome_is_valid = true;
+                res.microsteps = micro[row];
+                res.resolver_iterations = resolver[row];
+                res.error_flags = errors[row];
+            }
+        return r;
+    }
+    /* fks_policy_select: the selection of a policy table for a batch of configurations on the
+     * host, with the kernels' arithmetic and without a simulator (the planner's single query
+     * during real execution, QueryBestAction) */
+    static PolicySelection PolicySelect(const RobotDescription& robot, const PolicyTable& policy,
+                                        const std::vector<Configuration>& configs) {
+        const size_t W = (size_t)robot.ConfigurationWidth(), n = configs.size();
+        const FlatPolicyTable flat(policy, W);
+        std::vector<double> q(n * W);
+        for (size_t i = 0; i < n; ++i) {
+            if (configs[i].size() != W) throw std::invalid_argument("configuration has the wrong width");
+            std::copy(configs[i].begin(), configs[i].end(), q.begin() + i * W);
+        }
+        PolicySelection sel;
+        sel.choices.resize(n);
+        sel.distances.resize(n);
+        const fks_robot_desc d = robot.View();
+        const fks_status st = fks_policy_select(&d, &flat.table, q.data(), n, sel.choices.data(), sel.distances.data());
+        if (st != FKS_OK) throw SimulatorError(st, std::string("PolicySelect: ") + fks_status_string(st));
+        return sel;
     }
     /* Many independent calls in one launch (fks_forward_simulate_jobs; no reference counterpart:
      * the planner's stream of small ForwardSimulateRobots / ReverseSimulateRobots calls, whose

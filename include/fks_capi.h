@@ -464,6 +464,94 @@ fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* 
 fks_status fks_forward_simulate_path_jobs_device(fks_context* ctx, const fks_path_job* jobs, uint64_t num_jobs, void* stream,
                                                  int32_t synchronize);
 
+/* A policy table (added within ABI 10): the planner's execution policy as the roll-out reads it
+ * (SimulateExectionPolicy / QueryBestAction): M policy states, each with the configuration it
+ * stands for (its key) and its action, the configuration to move to next (its target).
+ * Selection of a configuration q:
+ *     p   = the position ResetPosition(q) leaves (joint limits clamped, continuous dofs and the
+ *           SE(2) angle wrapped), as every simulation call does to its starts
+ *     d_i = the robot's configuration distance from p to keys[i] (ComputeConfigurationDistanceTo,
+ *           the simulation shortcut's own arithmetic, SPCS:898, with the robot's distance_weights)
+ *     the choice is the i of the smallest d_i, compared with a strict < from +inf in ascending
+ *     i: the lowest index wins a tie, and a NaN distance never wins
+ *     no d_i < +inf, or d > max_distance            -> FKS_POLICY_LOST (tested first)
+ *     entry TERMINAL and d < terminal_distance      -> i | FKS_POLICY_ARRIVED (strict, as SPCS:899)
+ *     otherwise                                     -> i */
+#define FKS_POLICY_ENTRY_TERMINAL 0x1u
+typedef struct {
+    const double* keys;       /* [M][W]: the policy states' configurations */
+    const double* targets;    /* [M][W]: the action of each state: the next target */
+    const uint32_t* flags;    /* [M] FKS_POLICY_ENTRY_* bits, or NULL (= all 0) */
+    uint64_t num_entries;     /* M, 1 .. 2^30 */
+    double terminal_distance; /* arrived: the nearest entry is TERMINAL and d < this */
+    double max_distance;      /* lost: d > this (+inf: never) */
+} fks_policy_table;
+#define FKS_POLICY_ARRIVED 0x80000000u /* or-ed onto the entry's index */
+#define FKS_POLICY_LOST 0xFFFFFFFEu
+#define FKS_POLICY_NONE 0xFFFFFFFFu /* no selection: the particle had stopped */
+#define FKS_MAX_POLICY_ENTRIES (1ull << 30)
+/* The selection above for n configurations (configs [n][W]) on the host, without a context (as
+ * fks_robot_control_action): out_choice [n] (required) receives the verdicts, out_distance [n]
+ * (may be NULL) the chosen entry's d (+inf for a table without a finite distance).  The same
+ * expression trees as the policy kernels (shared SE(3) primitives and portable libm), so it is
+ * the planner's single query during real execution (QueryBestAction) and the host twin the
+ * roll-out's choices and distances equal bit for bit.  FKS_ERR_INVALID_ARGUMENT for a malformed
+ * robot or table (NULL keys or targets, M == 0 or above 2^30, a NaN distance) or a NULL configs
+ * or out_choice with n > 0. */
+fks_status fks_policy_select(const fks_robot_desc* robot, const fks_policy_table* table, const double* configs, uint64_t n,
+                             uint32_t* out_choice, double* out_distance);
+/* A batch rolled out under a policy table in one launch (added within ABI 10): closed loop, so
+ * two particles of one batch may take different routes.  With the context at call index c and
+ * K = max_legs, the call returns byte for byte what this sequence returns, and leaves the call
+ * index at c + K:
+ *     q_0 = starts; every particle active
+ *     leg k = 0 .. K-1:
+ *         every active particle p: choice[k][p], distance[k][p] = selection of q_k[p];
+ *             FKS_POLICY_LOST or ..._ARRIVED: p stops, legs_run[p] = k
+ *         the still-active particles, each under its own particle id, at call index c + k:
+ *             fks_forward_simulate(q_k[p] -> table.targets[choice[k][p]], allow_contacts)
+ *         q_{k+1}[p] = that call's position
+ *     particles that ran all K legs: legs_run[p] = K; choice[K][p], distance[K][p] = selection of q_K[p]
+ * Every leg begins with ResetPosition (controllers zeroed), and a leg that ends early (shortcut
+ * distance, failed resolve, contact with allow_contacts == 0, error bit) hands its configuration
+ * to the next selection, as a path's does.  A particle starts its next leg when its own leg
+ * ends: no leg waits for the batch.
+ * Outputs: the five simulation outputs are leg-major as a path's, out_positions [K][n][W]
+ * (required), the other four [K][n] (each may be NULL); out_choice uint32 [K+1][n] (required),
+ * out_distance double [K+1][n] and out_legs_run uint32 [n] (each may be NULL).  Rows a particle
+ * does not run (legs >= legs_run[p]) are defined: its position rows hold the bytes of the
+ * configuration handed over at the stop (q_{legs_run}[p], unchanged), so the last leg's slice
+ * always holds where the particle is; collided, microsteps, resolver iterations and error flags
+ * are 0; out_choice rows after row legs_run[p] are FKS_POLICY_NONE and their distance +inf.
+ * fks_get_statistics and the work counters of fks_get_last_call_counters grow by the sums of the
+ * simulated (particle, leg) pairs; `calls` counts 1 and `particles` those pairs.  n == 0 succeeds
+ * and consumes K call indices.
+ * Refused before anything is staged or counted, with the call index unchanged and the reason in
+ * fks_get_last_error: max_legs == 0, max_legs x segments per leg >= 2^31, M == 0 or M > 2^30,
+ * NULL keys or targets, a NULL out_choice or out_positions (or starts) with n > 0, a NaN
+ * terminal_distance or max_distance (FKS_ERR_INVALID_ARGUMENT); no robot set (FKS_ERR_NO_ROBOT); a
+ * context with fks_set_individual_jacobians on (FKS_ERR_UNSUPPORTED).
+ * The kernel is chosen as a path's over n: the small-batch policy kernel
+ * (FKS_KERNEL_POLICY_SMALL_BATCH) when n fits small_batch_resident_waves, no segments are set,
+ * the block is not lean and fks_set_small_batch_kernel is on; the throughput one
+ * (FKS_KERNEL_POLICY) otherwise.  fks_set_segment_steps / _policy / _heavy_relative apply as to a
+ * path; the call always runs these generic kernels, also when a batched shaped module exists.
+ * Host buffers: the table goes up with the starts in one copy and each output array comes down
+ * in one. */
+fks_status fks_forward_simulate_policy(fks_context* ctx, const double* starts, uint64_t n, const fks_policy_table* table,
+                                       uint64_t max_legs, int32_t allow_contacts, double* out_positions, uint8_t* out_collided,
+                                       uint32_t* out_microsteps, uint32_t* out_resolver_iterations, uint32_t* out_error_flags,
+                                       uint32_t* out_choice, double* out_distance, uint32_t* out_legs_run);
+/* Same with every pointer, the table's three included, in HBM (see fks_forward_simulate_device
+ * for stream and synchronize): rows [a, b) with first_particle_id = a equal the same rows of the
+ * whole call. */
+fks_status fks_forward_simulate_policy_device(fks_context* ctx, const double* d_starts, uint64_t n, const fks_policy_table* table,
+                                              uint64_t max_legs, uint64_t first_particle_id, int32_t allow_contacts,
+                                              double* d_out_positions, uint8_t* d_out_collided, uint32_t* d_out_microsteps,
+                                              uint32_t* d_out_resolver_iterations, uint32_t* d_out_error_flags,
+                                              uint32_t* d_out_choice, double* d_out_distance, uint32_t* d_out_legs_run,
+                                              void* stream, int32_t synchronize);
+
 /* CheckConfigCollision (SPCS:1398-1416) for a batch of n configurations (host
  * buffers): SetPosition(config), CheckEnvironmentCollision at threshold
  * inflation_ratio * res (SPCS:1403, 921-981) and CheckSelfCollisions at extended
@@ -612,8 +700,11 @@ typedef enum {
                                               particles together fit the small-batch kernel's resident waves */
     FKS_KERNEL_SHAPED_PATH_JOBS = 14,      /* fks_simulate_shaped_pj of the robot's batched module: a path, job
                                               or path-job batch (fks_prepare_batched_specialization) */
-    FKS_KERNEL_SHAPED_PATH_JOBS_SMALL_BATCH = 15 /* fks_simulate_shaped_pj_small: such a batch within the
-                                                    small-batch kernel's resident waves, once the module is built */
+    FKS_KERNEL_SHAPED_PATH_JOBS_SMALL_BATCH = 15, /* fks_simulate_shaped_pj_small: such a batch within the
+                                                     small-batch kernel's resident waves, once the module is built */
+    FKS_KERNEL_POLICY = 16,            /* fks_simulate_<family>[_lean]_policy (fks_forward_simulate_policy) */
+    FKS_KERNEL_POLICY_SMALL_BATCH = 17 /* fks_simulate_<family>_policy_small: a roll-out whose batch fits the
+                                          small-batch kernel's resident waves */
 } fks_kernel_kind;
 /* The launch layout fks_set_robot chose (ABI 8; diagnostic, no reference counterpart). */
 typedef struct fks_launch_info {
