@@ -368,6 +368,12 @@ PROTOTYPES = [
         [c_void_p, c_void_p, c_uint64, POINTER(PolicyTable), c_uint64, c_uint64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32],
     ),
+    ("fks_cluster_configs", c_int32, [POINTER(RobotDesc), POINTER(c_double), POINTER(c_uint64), c_uint64, c_double, POINTER(c_double),
+                                      POINTER(c_uint32), POINTER(c_uint32)]),
+    ("fks_cluster_configs_device", c_int32, [c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_double, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_int32]),
+    ("fks_cluster_configs_ctx", c_int32, [c_void_p, POINTER(c_double), POINTER(c_uint64), c_uint64, c_double, POINTER(c_double),
+                                          POINTER(c_uint32), POINTER(c_uint32)]),
     ("fks_forward_simulate_jobs", c_int32, [c_void_p, POINTER(Job), c_uint64]),
     ("fks_forward_simulate_jobs_device", c_int32, [c_void_p, POINTER(Job), c_uint64, c_void_p, c_int32]),
     ("fks_forward_simulate_path_jobs", c_int32, [c_void_p, POINTER(PathJob), c_uint64]),

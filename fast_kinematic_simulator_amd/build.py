@@ -13,8 +13,10 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SOURCES = ["csrc/fks_kernels.hip", "csrc/fks_capi.cpp", "csrc/fks_batch.cpp", "csrc/fks_multi.cpp", "csrc/fks_env_builder.cpp",
-           "csrc/fks_env_gpu.hip", "csrc/fks_robot_control.cpp", "csrc/fks_policy_select.cpp", "csrc/fks_specialize.cpp"]
-HEADERS = ["csrc/fks_batch.h", "csrc/fks_device.h", "csrc/fks_env_internal.h", "csrc/fks_se3.h", "csrc/fks_specialize.h",
+           "csrc/fks_env_gpu.hip", "csrc/fks_robot_control.cpp", "csrc/fks_policy_select.cpp", "csrc/fks_cluster.cpp",
+           "csrc/fks_specialize.cpp"]
+HEADERS = ["csrc/fks_batch.h", "csrc/fks_device.h", "csrc/fks_env_internal.h", "csrc/fks_host_distance.h", "csrc/fks_se3.h",
+           "csrc/fks_specialize.h",
            "../include/fks_capi.h", "../include/fks_portable_math.h", "../include/fks_control.h"]
 # the kernel source and the headers it includes, carried inside the library for the run-time
 # compilation of shape-specialised kernels (fks_specialize.cpp): name as included -> path
@@ -225,11 +227,35 @@ def build_policy_plan_test(force: bool = False) -> str:
     UndefinedBehaviorSanitizer, no HIP runtime and no libfks_hip.so, as build_batch_plan_test."""
     srcs = [os.path.join(ROOT, "tests", "cpp", "policy_plan_test.cpp"), os.path.join(PKG, "csrc", "fks_batch.cpp"),
             os.path.join(PKG, "csrc", "fks_policy_select.cpp")]
-    deps = srcs + [os.path.join(PKG, h) for h in ("csrc/fks_batch.h", "csrc/fks_device.h", "csrc/fks_se3.h", "../include/fks_capi.h",
-                                                  "../include/fks_portable_math.h")]
+    deps = srcs + [os.path.join(PKG, h) for h in ("csrc/fks_batch.h", "csrc/fks_device.h", "csrc/fks_host_distance.h", "csrc/fks_se3.h",
+                                                  "../include/fks_capi.h", "../include/fks_portable_math.h")]
     out_dir = os.path.join(ROOT, "build")
     os.makedirs(out_dir, exist_ok=True)
     target = os.path.join(out_dir, "policy_plan_test")
+    if not force and os.path.exists(target) and all(os.path.getmtime(target) >= os.path.getmtime(p) for p in deps):
+        return target
+    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "include")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-ffp-contract=off", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-D__HIP_PLATFORM_AMD__",
+           f"-I{os.path.join(ROOT, 'include')}", f"-I{os.path.join(PKG, 'csrc')}", f"-isystem{rocm_include}", *srcs, "-o", target]
+    proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if proc.returncode != 0:
+        raise RuntimeError("g++ failed:\n" + proc.stdout[-6000:])
+    return target
+
+
+def build_cluster_plan_test(force: bool = False) -> str:
+    """Compile tests/cpp/cluster_plan_test.cpp with csrc/fks_batch.cpp, csrc/fks_cluster.cpp and
+    csrc/fks_policy_select.cpp, the host-only plan of a clustering call and the host twin: g++ with
+    AddressSanitizer and UndefinedBehaviorSanitizer, no HIP runtime and no libfks_hip.so, as
+    build_policy_plan_test."""
+    srcs = [os.path.join(ROOT, "tests", "cpp", "cluster_plan_test.cpp"), os.path.join(PKG, "csrc", "fks_batch.cpp"),
+            os.path.join(PKG, "csrc", "fks_cluster.cpp"), os.path.join(PKG, "csrc", "fks_policy_select.cpp")]
+    deps = srcs + [os.path.join(PKG, h) for h in ("csrc/fks_batch.h", "csrc/fks_device.h", "csrc/fks_host_distance.h", "csrc/fks_se3.h",
+                                                  "../include/fks_capi.h", "../include/fks_portable_math.h")]
+    out_dir = os.path.join(ROOT, "build")
+    os.makedirs(out_dir, exist_ok=True)
+    target = os.path.join(out_dir, "cluster_plan_test")
     if not force and os.path.exists(target) and all(os.path.getmtime(target) >= os.path.getmtime(p) for p in deps):
         return target
     rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "include")
@@ -250,6 +276,16 @@ def build_policy_test(force: bool = False, workspace: bool = False) -> str:
         return build_cpp_program(os.path.join("tests", "cpp", "policy_interface_test.cpp"), "policy_interface_test_workspace",
                                  force, extra_flags=(f"-I{MOCK_WORKSPACE}",), extra_deps=_headers(MOCK_WORKSPACE))
     return build_cpp_program(os.path.join("tests", "cpp", "policy_interface_test.cpp"), "policy_interface_test", force)
+
+
+def build_cluster_test(force: bool = False, workspace: bool = False) -> str:
+    """Compile tests/cpp/cluster_interface_test.cpp: ClusterOutcomes of the plain class and of the
+    planner drop-in against the C-ABI entries on groups read from a file.  workspace=True puts the
+    mock planner workspace on the include path, as build_planner_test."""
+    if workspace:
+        return build_cpp_program(os.path.join("tests", "cpp", "cluster_interface_test.cpp"), "cluster_interface_test_workspace",
+                                 force, extra_flags=(f"-I{MOCK_WORKSPACE}",), extra_deps=_headers(MOCK_WORKSPACE))
+    return build_cpp_program(os.path.join("tests", "cpp", "cluster_interface_test.cpp"), "cluster_interface_test", force)
 
 
 def build_shaped_batches_test(force: bool = False) -> str:

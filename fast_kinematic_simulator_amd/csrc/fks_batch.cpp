@@ -343,3 +343,43 @@ void build_records(const Inputs& in, const Batch& b, double* seg_state, uint32_t
 }
 
 }  // namespace fks_batch
+
+namespace fks_batch {
+
+fks_status plan_cluster(ClusterPlan* p, const double* configs, const uint64_t* group_begin, uint64_t num_groups, double threshold,
+                        const void* out_distances, const void* out_labels, const void* out_num_clusters, std::string* why) {
+    *p = ClusterPlan();
+    auto refuse = [&](const char* text) {
+        *why = text;
+        return FKS_ERR_INVALID_ARGUMENT;
+    };
+    if (!(threshold == threshold)) return refuse("threshold is NaN");
+    if (!out_distances && !out_labels && !out_num_clusters) return refuse("no output: out_distances, out_labels and out_num_clusters are all NULL");
+    if (num_groups >= kMaxClusterConfigs) return refuse("at most 2^31-1 groups per call");
+    if (num_groups > 0 && !group_begin) return refuse("null group_begin");
+    p->num_groups = num_groups;
+    p->labelled = out_labels || out_num_clusters;
+    p->launch = num_groups > 0;
+    if (num_groups == 0) return FKS_OK;
+    /* every offset is checked before any is used: nothing is staged before a refusal */
+    for (uint64_t g = 0; g < num_groups; ++g)
+        if (group_begin[g + 1] < group_begin[g]) return refuse("group_begin must be ascending");
+    p->total = group_begin[num_groups];
+    if (p->total > kMaxClusterConfigs) return refuse("at most 2^31 configurations per call");
+    p->mat_begin.resize((size_t)num_groups + 1);
+    uint64_t words = 0;
+    for (uint64_t g = 0; g < num_groups; ++g) {
+        const uint64_t n = group_begin[g + 1] - group_begin[g]; /* <= 2^31: n x n fits 64 bits */
+        p->mat_begin[(size_t)g] = words;
+        p->largest = std::max(p->largest, n);
+        if (p->labelled && n > FKS_MAX_CLUSTER_GROUP) return refuse("a group with labels or counts holds at most FKS_MAX_CLUSTER_GROUP (256) configurations");
+        if (n > kMaxClusterMatrixWords || words + n * n > kMaxClusterMatrixWords) return refuse("the groups' matrices hold at most 2^27 doubles together");
+        words += n * n;
+    }
+    p->mat_begin[(size_t)num_groups] = words;
+    if (group_begin[num_groups] > group_begin[0] && !configs) return refuse("null configs");
+    if (p->labelled && p->largest > kClusterLdsGroup) p->work_words = words;
+    return FKS_OK;
+}
+
+}  // namespace fks_batch

@@ -123,6 +123,25 @@ RecordPlan plan_records(const Batch& b);
 void build_records(const Inputs& in, const Batch& b, double* seg_state, uint32_t* seg_done, const fksd::SimArgs* d_records,
                    fksd::SimArgs* h_records);
 
+/* The plan of a clustering call (fks_cluster_configs and its device entries): the groups' offsets
+ * checked, the prefix of their n x n matrices, and what the device call needs of its workspace.
+ * group_begin is read only when it is non-NULL and num_groups > 0; no other pointer is read. */
+struct ClusterPlan {
+    uint64_t num_groups = 0;
+    uint64_t total = 0;        /* N: configurations in all groups (group_begin[G] - group_begin[0] counted from 0) */
+    uint64_t largest = 0;      /* the largest group */
+    bool labelled = false;     /* labels or counts are asked for */
+    bool launch = false;       /* false: nothing to compute (no group, or only empty ones and no counts) */
+    std::vector<uint64_t> mat_begin; /* [G + 1]: group g's matrix at mat_begin[g] doubles; mat_begin[G] = sum of n^2 */
+    uint64_t work_words = 0;   /* doubles of the device's HBM link workspace (0: every labelled group's links fit LDS) */
+};
+constexpr uint64_t kMaxClusterMatrixWords = 1ull << 27;
+constexpr uint64_t kMaxClusterConfigs = 1ull << 31;
+/* groups of at most this many configurations keep their working link matrix in LDS (fks_kernels.hip) */
+constexpr uint64_t kClusterLdsGroup = 64;
+fks_status plan_cluster(ClusterPlan* p, const double* configs, const uint64_t* group_begin, uint64_t num_groups, double threshold,
+                        const void* out_distances, const void* out_labels, const void* out_num_clusters, std::string* why);
+
 }  // namespace fks_batch
 
 #endif

@@ -74,6 +74,9 @@ extern "C" __global__ void fks_simulate_se3_policy(const fksd::SimArgs* args, co
 extern "C" __global__ void fks_simulate_linked_policy_small(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
 extern "C" __global__ void fks_simulate_se2_policy_small(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
 extern "C" __global__ void fks_simulate_se3_policy_small(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
+extern "C" __global__ void fks_cluster_linked(const fksd::ClusterArgs args);
+extern "C" __global__ void fks_cluster_se2(const fksd::ClusterArgs args);
+extern "C" __global__ void fks_cluster_se3(const fksd::ClusterArgs args);
 extern "C" __global__ void fks_check_configs_linked(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se2(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se3(const fksd::SimArgs* args);
@@ -316,6 +319,17 @@ struct fks_context {
     uint32_t* d_policy_legs = nullptr;
     double* d_policy_in = nullptr; /* and its inputs' own: the starts with the table behind them */
     size_t cap_policy_sel = 0, cap_policy_in = 0;
+    /* fks_cluster_configs_device: the staged offsets (pinned, then in HBM) and the HBM link workspace ... */
+    uint64_t* h_cluster_off = nullptr;
+    uint64_t* d_cluster_off = nullptr;
+    double* d_cluster_work = nullptr;
+    size_t cap_cluster_off = 0, cap_cluster_work = 0;
+    /* ... and the host entry's staging: the configurations, the matrices, the labels and the counts */
+    double* d_cluster_in = nullptr;
+    double* d_cluster_mat = nullptr;
+    uint32_t* d_cluster_labels = nullptr;
+    uint32_t* d_cluster_counts = nullptr;
+    size_t cap_cluster_in = 0, cap_cluster_mat = 0, cap_cluster_labels = 0, cap_cluster_counts = 0;
     fksd::SimArgs* d_path_args = nullptr;     /* a batch's records (fks_batch::build_records): one per (job, leg) of
                                                  its normal form (a path's legs, a job batch's jobs), then job_first
                                                  and leg_first (SimArgs.job_first) */
@@ -323,7 +337,7 @@ struct fks_context {
     size_t cap_path_args = 0;
     std::vector<unsigned char> jobs_stage;    /* fks_forward_simulate_jobs / _path_jobs: the jobs' inputs, then outputs, end to end */
     bool pending = false;
-    int pending_kind = 0; /* 0 = forward simulation, 1 = batched config check */
+    int pending_kind = 0; /* 0 = forward simulation, 1 = batched config check, 2 = clustering (nothing to fold) */
     hipStream_t pending_stream = nullptr;
     fks_call_counters check_last;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -771,6 +785,13 @@ void fks_destroy(fks_context* ctx) {
     if (ctx->d_policy_distance) (void)hipFree(ctx->d_policy_distance);
     if (ctx->d_policy_legs) (void)hipFree(ctx->d_policy_legs);
     if (ctx->d_policy_in) (void)hipFree(ctx->d_policy_in);
+    if (ctx->h_cluster_off) (void)hipHostFree(ctx->h_cluster_off);
+    if (ctx->d_cluster_off) (void)hipFree(ctx->d_cluster_off);
+    if (ctx->d_cluster_work) (void)hipFree(ctx->d_cluster_work);
+    if (ctx->d_cluster_in) (void)hipFree(ctx->d_cluster_in);
+    if (ctx->d_cluster_mat) (void)hipFree(ctx->d_cluster_mat);
+    if (ctx->d_cluster_labels) (void)hipFree(ctx->d_cluster_labels);
+    if (ctx->d_cluster_counts) (void)hipFree(ctx->d_cluster_counts);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     delete ctx;
@@ -1278,6 +1299,7 @@ static fks_status settle(fks_context* ctx) {
     if (!ctx->pending) return FKS_OK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->pending_stream));
     ctx->pending = false;
+    if (ctx->pending_kind == 2) return FKS_OK; /* a clustering call: no counters, no statistics */
     const unsigned long long* c = ctx->h_counters;
     if (ctx->pending_kind == 1) {
         /* a config check: no simulator statistics, only its own counters */
@@ -2099,6 +2121,117 @@ fks_status fks_forward_simulate_policy(fks_context* ctx, const double* starts, u
     if (out_distance) HIP_TRY(ctx, hipMemcpy(out_distance, ctx->d_policy_distance, sel * sizeof(double), hipMemcpyDeviceToHost));
     if (out_legs_run) HIP_TRY(ctx, hipMemcpy(out_legs_run, ctx->d_policy_legs, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
+    return FKS_OK;
+}
+
+/* The clustering launch over device buffers: the offsets and the matrices' prefix go up in one
+ * pinned copy on the stream, one workgroup serves a group.  No call index, no counters. */
+static fks_status cluster_device(fks_context* ctx, const fks_batch::ClusterPlan& plan, const double* d_configs,
+                                 const uint64_t* group_begin, double threshold, double* d_out_distances, uint32_t* d_out_labels,
+                                 uint32_t* d_out_num_clusters, hipStream_t s, int32_t synchronize) {
+    if (!plan.launch) return FKS_OK;
+    const size_t G = (size_t)plan.num_groups, words = 2 * (G + 1);
+    if (words > ctx->cap_cluster_off) {
+        if (ctx->h_cluster_off) (void)hipHostFree(ctx->h_cluster_off);
+        ctx->h_cluster_off = nullptr;
+        ctx->cap_cluster_off = 0;
+        HIP_TRY(ctx, ensure(&ctx->d_cluster_off, words));
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_cluster_off, words * sizeof(uint64_t), 0));
+        ctx->cap_cluster_off = words;
+    }
+    if (plan.work_words > ctx->cap_cluster_work) {
+        HIP_TRY(ctx, ensure(&ctx->d_cluster_work, (size_t)plan.work_words));
+        ctx->cap_cluster_work = (size_t)plan.work_words;
+    }
+    /* the previous call has settled, so the pinned copy is free */
+    std::memcpy(ctx->h_cluster_off, group_begin, (G + 1) * sizeof(uint64_t));
+    std::memcpy(ctx->h_cluster_off + (G + 1), plan.mat_begin.data(), (G + 1) * sizeof(uint64_t));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cluster_off, ctx->h_cluster_off, words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    fksd::ClusterArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.R = ctx->R;
+    a.configs = d_configs;
+    a.offsets = ctx->d_cluster_off;
+    a.num_groups = plan.num_groups;
+    a.threshold = threshold;
+    a.out_distances = d_out_distances;
+    a.out_labels = d_out_labels;
+    a.out_num_clusters = d_out_num_clusters;
+    a.work = plan.work_words ? ctx->d_cluster_work : nullptr;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(plan.num_groups, 1u << 16);
+    void (*kernel)(const fksd::ClusterArgs) =
+        ctx->R.type == FKS_ROBOT_LINKED ? fks_cluster_linked : (ctx->R.type == FKS_ROBOT_SE2 ? fks_cluster_se2 : fks_cluster_se3);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(fksd::kClusterThreads), 0, s, a);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->pending = true;
+    ctx->pending_kind = 2;
+    ctx->pending_stream = s;
+    if (synchronize) return settle(ctx);
+    return FKS_OK;
+}
+
+/* what both context entries refuse, and the plan of what they run */
+static fks_status cluster_entry(fks_context* ctx, fks_batch::ClusterPlan* plan, const double* configs, const uint64_t* group_begin,
+                                uint64_t num_groups, double threshold, const void* out_distances, const void* out_labels,
+                                const void* out_num_clusters) {
+    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
+    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
+    std::string why;
+    const fks_status st =
+        fks_batch::plan_cluster(plan, configs, group_begin, num_groups, threshold, out_distances, out_labels, out_num_clusters, &why);
+    if (st != FKS_OK) return fail(ctx, st, why);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return settle(ctx);
+}
+
+fks_status fks_cluster_configs_device(fks_context* ctx, const double* d_configs, const uint64_t* group_begin, uint64_t num_groups,
+                                      double threshold, double* d_out_distances, uint32_t* d_out_labels,
+                                      uint32_t* d_out_num_clusters, void* stream, int32_t synchronize) {
+    fks_batch::ClusterPlan plan;
+    const fks_status st =
+        cluster_entry(ctx, &plan, d_configs, group_begin, num_groups, threshold, d_out_distances, d_out_labels, d_out_num_clusters);
+    if (st != FKS_OK) return st;
+    return cluster_device(ctx, plan, d_configs, group_begin, threshold, d_out_distances, d_out_labels, d_out_num_clusters,
+                          reinterpret_cast<hipStream_t>(stream), synchronize);
+}
+
+fks_status fks_cluster_configs_ctx(fks_context* ctx, const double* configs, const uint64_t* group_begin, uint64_t num_groups,
+                                   double threshold, double* out_distances, uint32_t* out_labels, uint32_t* out_num_clusters) {
+    fks_batch::ClusterPlan plan;
+    const fks_status st = cluster_entry(ctx, &plan, configs, group_begin, num_groups, threshold, out_distances, out_labels, out_num_clusters);
+    if (st != FKS_OK) return st;
+    if (!plan.launch) return FKS_OK;
+    const size_t W = (size_t)ctx->R.W, N = (size_t)plan.total, G = (size_t)plan.num_groups;
+    const size_t in_words = N * W, mat_words = (size_t)plan.mat_begin[G];
+    if (in_words > ctx->cap_cluster_in) {
+        HIP_TRY(ctx, ensure(&ctx->d_cluster_in, in_words));
+        ctx->cap_cluster_in = in_words;
+    }
+    if (out_distances && mat_words > ctx->cap_cluster_mat) {
+        HIP_TRY(ctx, ensure(&ctx->d_cluster_mat, mat_words));
+        ctx->cap_cluster_mat = mat_words;
+    }
+    if (out_labels && N > ctx->cap_cluster_labels) {
+        HIP_TRY(ctx, ensure(&ctx->d_cluster_labels, N));
+        ctx->cap_cluster_labels = N;
+    }
+    if (out_num_clusters && G > ctx->cap_cluster_counts) {
+        HIP_TRY(ctx, ensure(&ctx->d_cluster_counts, G));
+        ctx->cap_cluster_counts = G;
+    }
+    /* configs [N][W] goes up in one copy */
+    if (in_words && configs) HIP_TRY(ctx, hipMemcpy(ctx->d_cluster_in, configs, in_words * sizeof(double), hipMemcpyHostToDevice));
+    const fks_status run = cluster_device(ctx, plan, ctx->d_cluster_in, group_begin, threshold,
+                                          out_distances ? ctx->d_cluster_mat : nullptr, out_labels ? ctx->d_cluster_labels : nullptr,
+                                          out_num_clusters ? ctx->d_cluster_counts : nullptr, nullptr, 1);
+    if (run != FKS_OK) return run;
+    if (out_distances && mat_words)
+        HIP_TRY(ctx, hipMemcpy(out_distances, ctx->d_cluster_mat, mat_words * sizeof(double), hipMemcpyDeviceToHost));
+    /* labels before group_begin[0] belong to no group: the caller's stay as they are */
+    const size_t first = (size_t)group_begin[0];
+    if (out_labels && N > first)
+        HIP_TRY(ctx, hipMemcpy(out_labels + first, ctx->d_cluster_labels + first, (N - first) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_num_clusters) HIP_TRY(ctx, hipMemcpy(out_num_clusters, ctx->d_cluster_counts, G * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return FKS_OK;
 }
 

@@ -434,6 +434,25 @@ struct PolicyArgs {
     uint32_t* out_legs_run;
 };
 
+/* The argument of the clustering kernels (fks_cluster_configs_device, fks_cluster_<family>): passed
+ * by value.  offsets is the entry's staged copy of group_begin [G + 1] followed by the matrices'
+ * prefix mat_begin [G + 1] (fks_batch::ClusterPlan).  work is the HBM link workspace (group g's
+ * links at mat_begin[g]), NULL when every labelled group's links fit LDS. */
+constexpr int kClusterThreads = 256;   /* one workgroup per group */
+constexpr int kClusterLdsGroup = 64;   /* groups up to this keep their links in LDS (= fks_batch::kClusterLdsGroup) */
+constexpr int kClusterLdsConfigs = 4096; /* doubles of a group's configurations staged in LDS (larger groups read HBM) */
+struct ClusterArgs {
+    RobotDev R;
+    const double* configs;
+    const uint64_t* offsets;
+    uint64_t num_groups;
+    double threshold;
+    double* out_distances;
+    uint32_t* out_labels;
+    uint32_t* out_num_clusters;
+    double* work;
+};
+
 enum {
     kCntSuccessful = 0,
     kCntUnsuccessful,

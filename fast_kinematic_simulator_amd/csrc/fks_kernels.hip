@@ -4781,6 +4781,183 @@ extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_policy_small(
 #endif /* FKS_SHAPE_L */
 
 #if !defined(FKS_SHAPE_L)
+/* Outcome clustering (fks_cluster_configs_device; the host twin is fks_cluster_configs, the
+ * definition is in fks_capi.h): one workgroup of kClusterThreads per group, groups strided over
+ * the grid.
+ *   matrix   the n (n - 1) / 2 pairs i < j are spread over the threads (rows r and n - 1 - r, or
+ *            n - 2 - r for odd n, are laid end to end, so every thread index is a pair); a pair's
+ *            distance is config_distance_of<RT> with cfg = c_i, target = c_j, stored to M[i][j] and
+ *            mirrored to M[j][i].  The group's configurations are staged in LDS when they fit
+ *            kClusterLdsConfigs doubles and read through the cache otherwise.
+ *   links    the working link matrix L (upper triangle, +inf for whatever is not < +inf) lies in
+ *            LDS for n <= kClusterLdsGroup and in the context's HBM workspace above that.
+ *   scan     wave w takes live rows a = w, w + 4, ..., its lanes the live columns b = a + 1 + ln,
+ *            + 64, ...: a thread meets its pairs in ascending (a, b), so a strict < from +inf keeps
+ *            its lowest pair of its smallest link and +inf never wins; the butterfly and the four
+ *            waves' results then reduce by (smaller L, then smaller a, then smaller b), which is
+ *            the ascending scan's answer whatever the thread count (as policy_select's over (d, i)).
+ *   merge    thread k folds L(b, k) into L(a, k) by max, renames b's members and retires b. */
+constexpr uint32_t kClusterNone = 0xFFFFFFFFu;
+template <int RT>
+__device__ __forceinline__ void cluster_groups(const ClusterArgs& A) {
+    constexpr int NT = kClusterThreads, NW = kClusterThreads / kWave;
+    __shared__ double s_link[kClusterLdsGroup * kClusterLdsGroup];
+    __shared__ double s_cfg[kClusterLdsConfigs];
+    __shared__ double s_joints[kJointWords * kMaxJoints];
+    __shared__ int32_t s_dofj[kMaxDofs];
+    __shared__ double s_red_l[NW];
+    __shared__ uint32_t s_red_a[NW], s_red_b[NW];
+    __shared__ uint32_t s_name[FKS_MAX_CLUSTER_GROUP], s_alive[FKS_MAX_CLUSTER_GROUP];
+    const RobotDev& R = A.R;
+    const uint32_t W = (uint32_t)R.W;
+    const uint32_t tid = threadIdx.x, ln = (uint32_t)lane_id(), wv = tid >> 6;
+    const double inf = __builtin_inf();
+    const JointDev* joints = R.joints;
+    const int32_t* dofj = R.dof_joint;
+    if constexpr (RT == FKS_ROBOT_LINKED) {
+        /* the robot tables the distance reads, once per workgroup */
+        if (R.J <= kMaxJoints && R.D <= kMaxDofs) {
+            const double* sj = reinterpret_cast<const double*>(R.joints);
+            for (uint32_t k = tid; k < (uint32_t)(R.J * kJointWords); k += NT) s_joints[k] = gp(sj)[k];
+            for (uint32_t k = tid; k < (uint32_t)R.D; k += NT) s_dofj[k] = gp(R.dof_joint)[k];
+            joints = reinterpret_cast<const JointDev*>(s_joints);
+            dofj = s_dofj;
+        }
+    }
+    const uint64_t G = A.num_groups;
+    const FKS_GLOBAL uint64_t* gb = gp(A.offsets);
+    const FKS_GLOBAL uint64_t* mb = gb + (G + 1);
+    for (uint64_t g = blockIdx.x; g < G; g += gridDim.x) {
+        const uint64_t first = gb[g], mat = mb[g];
+        const uint32_t n = (uint32_t)(gb[g + 1] - first); /* n x n <= 2^27 (fks_batch::plan_cluster) */
+        double* M = A.out_distances ? A.out_distances + mat : nullptr;
+        double* L = nullptr;
+        if ((A.out_labels || A.out_num_clusters) && n <= FKS_MAX_CLUSTER_GROUP)
+            L = (n <= (uint32_t)kClusterLdsGroup) ? s_link : (A.work ? A.work + mat : nullptr);
+        const bool labelled = L != nullptr;
+        const double* C = A.configs + first * W;
+        if (n * W <= (uint32_t)kClusterLdsConfigs) {
+            for (uint32_t k = tid; k < n * W; k += NT) s_cfg[k] = gp(C)[k];
+            C = s_cfg;
+        }
+        if (labelled)
+            for (uint32_t k = tid; k < n; k += NT) {
+                s_name[k] = k;
+                s_alive[k] = 1u;
+            }
+        __syncthreads();
+        if (n >= 2) {
+            const uint32_t odd = n & 1u;
+            const uint32_t rows = (n - odd) / 2, width = n - 1 + odd; /* rows x width = n (n - 1) / 2 */
+            for (uint32_t t = tid; t < rows * width; t += NT) {
+                const uint32_t r = t / width, c = t - r * width, len = n - 1 - r;
+                uint32_t i, j;
+                if (c < len) {
+                    i = r;
+                    j = r + 1 + c;
+                } else {
+                    i = n - 1 - odd - r;
+                    j = i + 1 + (c - len);
+                }
+                const double d = config_distance_of<RT>(R, joints, dofj, C + (size_t)i * W, C + (size_t)j * W);
+                if (M) {
+                    gpw(M)[(uint64_t)i * n + j] = d;
+                    gpw(M)[(uint64_t)j * n + i] = d;
+                }
+                if (labelled) L[i * n + j] = (d < inf) ? d : inf;
+            }
+        }
+        if (M)
+            for (uint32_t k = tid; k < n; k += NT) gpw(M)[(uint64_t)k * n + k] = 0.0;
+        if (labelled) {
+            __syncthreads();
+            for (;;) {
+                double best = inf;
+                uint32_t ba = kClusterNone, bb = kClusterNone;
+                for (uint32_t a = wv; a + 1 < n; a += NW) {
+                    if (!s_alive[a]) continue;
+                    for (uint32_t b = a + 1 + ln; b < n; b += kWave) {
+                        if (!s_alive[b]) continue;
+                        const double l = L[a * n + b];
+                        if (l < best) {
+                            best = l;
+                            ba = a;
+                            bb = b;
+                        }
+                    }
+                }
+                /* a thread without a pair holds (+inf, NONE, NONE) */
+#pragma unroll
+                for (int m = 1; m < kWave; m <<= 1) {
+                    const double ol = __shfl_xor(best, m, kWave);
+                    const uint32_t oa = (uint32_t)__shfl_xor((int)ba, m, kWave);
+                    const uint32_t ob = (uint32_t)__shfl_xor((int)bb, m, kWave);
+                    if (ol < best || (ol == best && (oa < ba || (oa == ba && ob < bb)))) {
+                        best = ol;
+                        ba = oa;
+                        bb = ob;
+                    }
+                }
+                if (ln == 0) {
+                    s_red_l[wv] = best;
+                    s_red_a[wv] = ba;
+                    s_red_b[wv] = bb;
+                }
+                __syncthreads();
+                best = s_red_l[0];
+                ba = s_red_a[0];
+                bb = s_red_b[0];
+                for (int w = 1; w < NW; ++w) {
+                    const double ol = s_red_l[w];
+                    const uint32_t oa = s_red_a[w], ob = s_red_b[w];
+                    if (ol < best || (ol == best && (oa < ba || (oa == ba && ob < bb)))) {
+                        best = ol;
+                        ba = oa;
+                        bb = ob;
+                    }
+                }
+                /* workgroup-uniform: every thread read the same four results */
+                if (ba == kClusterNone || best > A.threshold) break;
+                for (uint32_t k = tid; k < n; k += NT) {
+                    if (k == bb) {
+                        s_alive[k] = 0u; /* read by its own thread alone in this phase */
+                    } else if (k != ba && s_alive[k]) {
+                        const uint32_t u = (k < ba) ? k * n + ba : ba * n + k;
+                        const uint32_t v = (k < bb) ? k * n + bb : bb * n + k;
+                        const double lak = L[u], lbk = L[v];
+                        L[u] = (lbk > lak) ? lbk : lak;
+                    }
+                    if (s_name[k] == bb) s_name[k] = ba;
+                }
+                __syncthreads();
+            }
+            /* numbered in ascending order of the smallest member */
+            if (A.out_labels)
+                for (uint32_t k = tid; k < n; k += NT) {
+                    const uint32_t nm = s_name[k];
+                    uint32_t c = 0;
+                    for (uint32_t q = 0; q < nm; ++q) c += s_alive[q];
+                    gpw(A.out_labels)[first + k] = c;
+                }
+            if (A.out_num_clusters && tid == 0) {
+                uint32_t c = 0;
+                for (uint32_t q = 0; q < n; ++q) c += s_alive[q];
+                gpw(A.out_num_clusters)[g] = c;
+            }
+        }
+        __syncthreads(); /* the next group reuses the LDS arrays */
+    }
+}
+extern "C" __global__ void __launch_bounds__(kClusterThreads) fks_cluster_linked(const ClusterArgs args) {
+    cluster_groups<FKS_ROBOT_LINKED>(args);
+}
+extern "C" __global__ void __launch_bounds__(kClusterThreads) fks_cluster_se2(const ClusterArgs args) {
+    cluster_groups<FKS_ROBOT_SE2>(args);
+}
+extern "C" __global__ void __launch_bounds__(kClusterThreads) fks_cluster_se3(const ClusterArgs args) {
+    cluster_groups<FKS_ROBOT_SE3>(args);
+}
+
 /* device self-test of the portable libm (fks_selftest_math) */
 extern "C" __global__ void fks_math_probe(const double* a, const double* b, double* out, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -663,6 +663,87 @@ class HipParticleContactSimulator:
                                                              1 if synchronize else 0)
         _capi.check(st, self._ctx, "fks_forward_simulate_path_jobs_device")
 
+    def cluster_outcomes(self, robot: RobotDescription, groups, threshold: float, distances: bool = False) -> dict:
+        """fks_cluster_configs_ctx: the complete-link clusters of each group of configurations under
+        `threshold` by the robot's configuration distance, in one launch (include/fks_capi.h).
+        groups is a sequence of (n_g, W) arrays.  Returns per group "labels" (uint32 [n_g]), "counts"
+        uint32 [G] and, with distances=True, "distances" (a list of (n_g, n_g) arrays)."""
+        self.set_robot(robot)
+        configs, begin = _cluster_groups(groups, robot.config_width)
+        out = _cluster_outputs(begin, True, distances)
+        st = self._lib.fks_cluster_configs_ctx(self._ctx, _cluster_ptr(configs, ctypes.c_double), _capi.as_ptr(begin, ctypes.c_uint64),
+                                               len(begin) - 1, float(threshold), _cluster_ptr(out[0], ctypes.c_double),
+                                               _cluster_ptr(out[1], ctypes.c_uint32), _cluster_ptr(out[2], ctypes.c_uint32))
+        _capi.check(st, self._ctx, "fks_cluster_configs_ctx")
+        return _cluster_result(begin, *out)
+
+    def cluster_outcomes_device(self, robot: RobotDescription, d_configs, group_begin, threshold: float, d_out_distances=0,
+                                d_out_labels=0, d_out_num_clusters=0, stream=0, synchronize=False):
+        """fks_cluster_configs_device: d_configs is a device pointer (int), e.g. the data_ptr() of
+        the tensor a jobs call wrote its positions to; group_begin the G + 1 ascending offsets (in
+        configurations, a host sequence); the three outputs device pointers (each may be 0, not
+        all): doubles [sum of n_g^2], uint32 [N] and uint32 [G]."""
+        self.set_robot(robot)
+        begin = np.ascontiguousarray(np.asarray(group_begin, dtype=np.uint64).reshape(-1))
+        if begin.size == 0:
+            begin = np.zeros(1, dtype=np.uint64)
+        st = self._lib.fks_cluster_configs_device(
+            self._ctx, ctypes.c_void_p(d_configs or None), _capi.as_ptr(begin, ctypes.c_uint64), begin.size - 1, float(threshold),
+            ctypes.c_void_p(d_out_distances or None), ctypes.c_void_p(d_out_labels or None),
+            ctypes.c_void_p(d_out_num_clusters or None), ctypes.c_void_p(stream or None), 1 if synchronize else 0)
+        _capi.check(st, self._ctx, "fks_cluster_configs_device")
+
+
+def _cluster_groups(groups, W: int):
+    """configs (N, W) and group_begin uint64 [G + 1] of a sequence of (n_g, W) arrays"""
+    arrays = [np.asarray(g, dtype=np.float64).reshape(-1, W) for g in groups]
+    begin = np.zeros(len(arrays) + 1, dtype=np.uint64)
+    if arrays:
+        begin[1:] = np.cumsum([a.shape[0] for a in arrays], dtype=np.uint64)
+    configs = np.ascontiguousarray(np.concatenate(arrays, axis=0)) if arrays else np.zeros((0, W), dtype=np.float64)
+    return configs, begin
+
+
+def _cluster_ptr(array, ctype):
+    return _capi.as_ptr(array, ctype) if array is not None and array.size else None
+
+
+def _cluster_outputs(begin, labels: bool, distances: bool):
+    sizes = np.diff(begin).astype(np.uint64)
+    mats = np.zeros(max(int((sizes * sizes).sum()), 1), dtype=np.float64) if distances else None
+    lab = np.zeros(max(int(begin[-1]), 1), dtype=np.uint32) if labels else None
+    cnt = np.zeros(max(len(begin) - 1, 1), dtype=np.uint32) if labels else None
+    return mats, lab, cnt
+
+
+def _cluster_result(begin, mats, lab, cnt) -> dict:
+    G = len(begin) - 1
+    sizes = [int(begin[g + 1] - begin[g]) for g in range(G)]
+    out = {}
+    if lab is not None:
+        out["labels"] = [lab[int(begin[g]):int(begin[g + 1])].copy() for g in range(G)]
+        out["counts"] = cnt[:G].copy()
+    if mats is not None:
+        out["distances"], at = [], 0
+        for n in sizes:
+            out["distances"].append(mats[at:at + n * n].reshape(n, n).copy())
+            at += n * n
+    return out
+
+
+def cluster_outcomes_host(robot: RobotDescription, groups, threshold: float, distances: bool = False, labels: bool = True) -> dict:
+    """fks_cluster_configs: the host twin of Simulator.cluster_outcomes, with the kernels'
+    arithmetic and without a context or a GPU; the same result byte for byte."""
+    configs, begin = _cluster_groups(groups, robot.config_width)
+    out = _cluster_outputs(begin, labels, distances)
+    desc, keep = robot.to_c()
+    st = _capi.lib().fks_cluster_configs(ctypes.byref(desc), _cluster_ptr(configs, ctypes.c_double), _capi.as_ptr(begin, ctypes.c_uint64),
+                                         len(begin) - 1, float(threshold), _cluster_ptr(out[0], ctypes.c_double),
+                                         _cluster_ptr(out[1], ctypes.c_uint32), _cluster_ptr(out[2], ctypes.c_uint32))
+    del keep
+    _capi.check(st, None, "fks_cluster_configs")
+    return _cluster_result(begin, *out)
+
 
 @dataclass
 class PolicyTable:

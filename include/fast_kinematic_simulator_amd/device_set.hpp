@@ -188,6 +188,16 @@ class DeviceSet {
               ctx_, what);
     }
 
+    /* the groups' distance matrices and complete-link clusters in one launch
+     * (fks_cluster_configs_ctx, host buffers, its arguments): on devices[0] alone, whatever the
+     * groups' sizes (a group is one workgroup's work; there is no fks_multi_* clustering).  Not a
+     * batch of the simulation: call index, statistics and last_devices() stay as they are */
+    void cluster_configs(const double* configs, const uint64_t* group_begin, uint64_t num_groups, double threshold,
+                         double* out_distances, uint32_t* out_labels, uint32_t* out_num_clusters, const char* what) {
+        Check(fks_cluster_configs_ctx(ctx_, configs, group_begin, num_groups, threshold, out_distances, out_labels, out_num_clusters),
+              ctx_, what);
+    }
+
     /* many independent calls in one launch per device (fks_forward_simulate_jobs, host
      * buffers); the devices are chosen from the jobs' particles together as for simulate() */
     void simulate_jobs(const fks_job* jobs, uint64_t num_jobs, const char* what) {

@@ -363,6 +363,35 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
         for (const auto& c : configs) flat.push_back(robot.ToFlat(c));
         return fks::HipParticleContactSimulator::PolicySelect(robot.HipDescription(), FlatPolicy(robot, policy), flat);
     }
+    /* Not part of SimulatorInterface: the planner's step after every forward batch
+     * (fks_cluster_configs_ctx).  Each group's outcomes (one group per job) are clustered by the
+     * robot's configuration distance, complete link under `threshold`, in one launch on
+     * devices[0]; every cluster becomes a child state.  No call index is consumed. */
+    fks::OutcomeClusters ClusterOutcomes(const std::shared_ptr<BaseRobotType>& immutable_robot,
+                                         const std::vector<std::vector<Configuration, ConfigAlloc>>& groups, const double threshold,
+                                         const bool want_distances = false) {
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        SetRobot(robot);
+        fks::FlatClusterGroups flat(FlatGroups(robot, groups), (size_t)robot.HipDescription().ConfigurationWidth(), want_distances);
+        dev_->cluster_configs(flat.configs.data(), flat.begin.data(), groups.size(), threshold, flat.matrices_or_null(), flat.labels_ptr(),
+                              flat.counts_ptr(), "ClusterOutcomes");
+        return flat.result(want_distances);
+    }
+    /* fks_cluster_configs on the host, without a simulator: the same result byte for byte */
+    static fks::OutcomeClusters ClusterOutcomesHost(const std::shared_ptr<BaseRobotType>& immutable_robot,
+                                                    const std::vector<std::vector<Configuration, ConfigAlloc>>& groups,
+                                                    const double threshold, const bool want_distances = false) {
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        return fks::HipParticleContactSimulator::ClusterOutcomesHost(robot.HipDescription(), FlatGroups(robot, groups), threshold,
+                                                                     want_distances);
+    }
+    static std::vector<std::vector<fks::Configuration>> FlatGroups(const DerivedRobotType& robot,
+                                                                   const std::vector<std::vector<Configuration, ConfigAlloc>>& groups) {
+        std::vector<std::vector<fks::Configuration>> flat(groups.size());
+        for (size_t g = 0; g < groups.size(); ++g)
+            for (const auto& c : groups[g]) flat[g].push_back(robot.ToFlat(c));
+        return flat;
+    }
     /* Not part of SimulatorInterface: many independent calls in one launch
      * (fks_forward_simulate_jobs), for the planner's stream of small ForwardSimulateRobots /
      * ReverseSimulateRobots calls (their semantics are the same, SPCS:838-841).  A job is one

@@ -92,6 +92,54 @@ struct PolicySelection {
     std::vector<uint32_t> choices;
     std::vector<double> distances;
 };
+/* What ClusterOutcomes returns: per group the cluster number of every configuration (clusters
+ * numbered in ascending order of their smallest member), the number of clusters and, when asked
+ * for, the row-major n x n matrix of configuration distances (fks_cluster_configs in fks_capi.h) */
+struct OutcomeClusters {
+    std::vector<std::vector<uint32_t>> labels;
+    std::vector<uint32_t> counts;
+    std::vector<std::vector<double>> distances;
+};
+/* groups of configurations laid end to end for fks_cluster_configs, and the result taken apart */
+struct FlatClusterGroups {
+    std::vector<double> configs;
+    std::vector<uint64_t> begin;
+    std::vector<double> matrices;
+    std::vector<uint32_t> labels, counts;
+    FlatClusterGroups(const std::vector<std::vector<Configuration>>& groups, size_t W, bool want_distances) : begin(groups.size() + 1, 0) {
+        size_t words = 0;
+        for (size_t g = 0; g < groups.size(); ++g) {
+            for (const Configuration& c : groups[g]) {
+                if (c.size() != W) throw std::invalid_argument("configuration has the wrong width");
+                configs.insert(configs.end(), c.begin(), c.end());
+            }
+            begin[g + 1] = begin[g] + groups[g].size();
+            words += groups[g].size() * groups[g].size();
+        }
+        if (want_distances) matrices.resize(words);
+        labels.resize((size_t)begin.back());
+        counts.resize(groups.size());
+    }
+    double* matrices_or_null() { return matrices.empty() ? nullptr : matrices.data(); }
+    /* (one word past the end for empty vectors: fks_cluster_configs takes NULL as "not asked for") */
+    uint32_t* labels_ptr() { return labels.empty() ? &spare_ : labels.data(); }
+    uint32_t* counts_ptr() { return counts.empty() ? &spare_ : counts.data(); }
+    OutcomeClusters result(bool want_distances) const {
+        OutcomeClusters r;
+        r.counts = counts;
+        size_t at = 0;
+        for (size_t g = 0; g + 1 < begin.size(); ++g) {
+            const size_t n = (size_t)(begin[g + 1] - begin[g]);
+            r.labels.emplace_back(labels.begin() + (size_t)begin[g], labels.begin() + (size_t)begin[g + 1]);
+            if (want_distances) r.distances.emplace_back(matrices.begin() + at, matrices.begin() + at + n * n);
+            at += n * n;
+        }
+        return r;
+    }
+
+  private:
+    uint32_t spare_ = 0;
+};
 /* What ForwardSimulateRobotsUnderPolicy returns: results[leg][particle] as a path's (a leg a
  * particle did not run holds the configuration it stopped at and no contact; target_config is
  * the chosen entry's action, or the configuration itself for such a leg), choices and distances
@@ -545,6 +593,28 @@ class HipParticleContactSimulator {
         const fks_status st = fks_policy_select(&d, &flat.table, q.data(), n, sel.choices.data(), sel.distances.data());
         if (st != FKS_OK) throw SimulatorError(st, std::string("PolicySelect: ") + fks_status_string(st));
         return sel;
+    }
+    /* The planner's step after every forward batch (fks_cluster_configs_ctx): each group's
+     * outcomes (one group per job) clustered by the robot's configuration distance, complete link
+     * under `threshold`, in one launch.  Byte for byte what ClusterOutcomesHost returns; no call
+     * index is consumed and no statistics move. */
+    OutcomeClusters ClusterOutcomes(const RobotDescription& immutable_robot, const std::vector<std::vector<Configuration>>& groups,
+                                    double threshold, bool want_distances = false) {
+        SetRobot(immutable_robot);
+        FlatClusterGroups flat(groups, (size_t)immutable_robot.ConfigurationWidth(), want_distances);
+        dev_.cluster_configs(flat.configs.data(), flat.begin.data(), groups.size(), threshold, flat.matrices_or_null(), flat.labels_ptr(),
+                             flat.counts_ptr(), "ClusterOutcomes");
+        return flat.result(want_distances);
+    }
+    /* fks_cluster_configs: the same on the host, with the kernels' arithmetic and without a simulator */
+    static OutcomeClusters ClusterOutcomesHost(const RobotDescription& robot, const std::vector<std::vector<Configuration>>& groups,
+                                               double threshold, bool want_distances = false) {
+        FlatClusterGroups flat(groups, (size_t)robot.ConfigurationWidth(), want_distances);
+        const fks_robot_desc d = robot.View();
+        const fks_status st = fks_cluster_configs(&d, flat.configs.data(), flat.begin.data(), groups.size(), threshold,
+                                                  flat.matrices_or_null(), flat.labels_ptr(), flat.counts_ptr());
+        if (st != FKS_OK) throw SimulatorError(st, std::string("ClusterOutcomesHost: ") + fks_status_string(st));
+        return flat.result(want_distances);
     }
     /* Many independent calls in one launch (fks_forward_simulate_jobs; no reference counterpart:
      * the planner's stream of small ForwardSimulateRobots / ReverseSimulateRobots calls, whose

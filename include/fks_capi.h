@@ -552,6 +552,60 @@ fks_status fks_forward_simulate_policy_device(fks_context* ctx, const double* d_
                                               uint32_t* d_out_choice, double* d_out_distance, uint32_t* d_out_legs_run,
                                               void* stream, int32_t synchronize);
 
+/* Outcome clustering (added within ABI 10): the planner's step after every forward batch.  G
+ * groups of configurations go in, one group per job, as a batched call wrote them; each group's
+ * configuration-distance matrix and its complete-link clusters under `threshold` come out.
+ * group_begin holds G + 1 ascending offsets (in configurations) into configs [N][W], N =
+ * group_begin[G]; group g is configurations [group_begin[g], group_begin[g + 1]), n of them.  The
+ * configurations are taken as the bytes given: no ResetPosition, no clamping.
+ *
+ * Matrix of a group (row-major n x n doubles; the groups' matrices lie end to end, group g at the
+ * sum of n_h^2 over h < g): for i < j, M[i][j] is the robot's configuration distance
+ * (ComputeConfigurationDistanceTo) with cfg = c_i and target = c_j, in the arithmetic of the
+ * kernels' distance (wrap of continuous dofs and of the SE(2) angle inside the difference, the
+ * distance_weights, the SE(3) form through inverse / compose / log).  M[j][i] is the same bits:
+ * mirrored, never computed as c_j -> c_i (the SE(3) distance is not bitwise symmetric).  M[i][i]
+ * is +0.0.
+ *
+ * Clustering of a group: complete link, this library's statement (the planner's
+ * arc_utilities/simple_hierarchical_clustering.hpp is not pinned against it).  For the clustering
+ * only, a distance that is not < +inf (NaN, inf) counts as +inf.  Start with n singletons; a
+ * cluster is named by its smallest member; the link of two clusters is L(a, b) = max of M[i][j]
+ * over i in a, j in b.  Repeat: scan the live pairs (a, b), a < b, in ascending lexicographic
+ * order and keep the smallest L under a strict < starting from +inf (the lowest pair wins a tie,
+ * a +inf pair never wins); stop if no pair was kept or its L > threshold; otherwise merge b into a
+ * (L <= threshold merges, equality included), with L(a u b, k) = max(L(a, k), L(b, k)), which is
+ * exact.  The labels therefore depend on the matrix's bits and these rules alone.  Clusters are
+ * numbered 0, 1, ... in ascending order of their smallest member: out_labels[i] (i an index into
+ * configs) is its cluster's number within its group, out_num_clusters[g] the group's count (0 for
+ * an empty group).  A negative threshold merges nothing, +inf merges every finite pair.
+ *
+ * out_distances, out_labels [N] and out_num_clusters [G] may each be NULL, not all three.  When
+ * labels or counts are asked for, a group holds at most FKS_MAX_CLUSTER_GROUP configurations; with
+ * both NULL only the matrices are made and that bound is lifted.  Refused with
+ * FKS_ERR_INVALID_ARGUMENT, before anything is staged: a NaN threshold, all three outputs NULL,
+ * 2^31 groups or more, NULL group_begin with G > 0, non-ascending offsets, N above 2^31, a
+ * labelled group above the bound, a sum of n^2 above 2^27 doubles, NULL configs with N > 0, a
+ * malformed robot (host twin); FKS_ERR_NO_ROBOT for a context without a robot.  The device entries
+ * word every refusal in fks_get_last_error.  Empty groups and G == 0 succeed. */
+#define FKS_MAX_CLUSTER_GROUP 256
+/* The host twin: no context, no GPU.  The device entries below equal it byte for byte. */
+fks_status fks_cluster_configs(const fks_robot_desc* robot, const double* configs, const uint64_t* group_begin,
+                               uint64_t num_groups, double threshold, double* out_distances, uint32_t* out_labels,
+                               uint32_t* out_num_clusters);
+/* The same in one launch for the context's robot.  group_begin is a host array, staged by the
+ * entry; every other pointer is in HBM (d_configs may be the output buffer of a batched call on
+ * the same stream).  Stream and synchronize as fks_forward_simulate_device.  The call consumes no
+ * call index and touches no statistics, work counters or last-call counters.  A working link
+ * matrix of a group above 64 configurations lies in a workspace the context owns, grown on demand
+ * and freed with the context. */
+fks_status fks_cluster_configs_device(fks_context* ctx, const double* d_configs, const uint64_t* group_begin, uint64_t num_groups,
+                                      double threshold, double* d_out_distances, uint32_t* d_out_labels,
+                                      uint32_t* d_out_num_clusters, void* stream, int32_t synchronize);
+/* The same on host buffers: one upload, one download per output array. */
+fks_status fks_cluster_configs_ctx(fks_context* ctx, const double* configs, const uint64_t* group_begin, uint64_t num_groups,
+                                   double threshold, double* out_distances, uint32_t* out_labels, uint32_t* out_num_clusters);
+
 /* CheckConfigCollision (SPCS:1398-1416) for a batch of n configurations (host
  * buffers): SetPosition(config), CheckEnvironmentCollision at threshold
  * inflation_ratio * res (SPCS:1403, 921-981) and CheckSelfCollisions at extended
