@@ -15,8 +15,8 @@ ROOT = os.path.dirname(PKG)
 SOURCES = ["csrc/fks_kernels.hip", "csrc/fks_capi.cpp", "csrc/fks_batch.cpp", "csrc/fks_multi.cpp", "csrc/fks_env_builder.cpp",
            "csrc/fks_env_gpu.hip", "csrc/fks_robot_control.cpp", "csrc/fks_policy_select.cpp", "csrc/fks_cluster.cpp",
            "csrc/fks_specialize.cpp"]
-HEADERS = ["csrc/fks_batch.h", "csrc/fks_device.h", "csrc/fks_env_internal.h", "csrc/fks_host_distance.h", "csrc/fks_se3.h",
-           "csrc/fks_specialize.h",
+HEADERS = ["csrc/fks_batch.h", "csrc/fks_buffers.h", "csrc/fks_device.h", "csrc/fks_env_internal.h", "csrc/fks_host_distance.h",
+           "csrc/fks_se3.h", "csrc/fks_specialize.h",
            "../include/fks_capi.h", "../include/fks_portable_math.h", "../include/fks_control.h"]
 # the kernel source and the headers it includes, carried inside the library for the run-time
 # compilation of shape-specialised kernels (fks_specialize.cpp): name as included -> path
@@ -199,16 +199,19 @@ def build_path_jobs_test(force: bool = False) -> str:
     return build_cpp_program(os.path.join("tests", "cpp", "path_jobs_interface_test.cpp"), "path_jobs_interface_test", force)
 
 
-def build_batch_plan_test(force: bool = False) -> str:
-    """Compile tests/cpp/batch_plan_test.cpp with csrc/fks_batch.cpp, the host-only plan of batched
-    calls: g++ with AddressSanitizer and UndefinedBehaviorSanitizer, no HIP runtime and no
-    libfks_hip.so (ROCm's include path only for the vector types SimArgs names)."""
-    srcs = [os.path.join(ROOT, "tests", "cpp", "batch_plan_test.cpp"), os.path.join(PKG, "csrc", "fks_batch.cpp")]
-    deps = srcs + [os.path.join(PKG, h) for h in ("csrc/fks_batch.h", "csrc/fks_device.h", "../include/fks_capi.h",
-                                                  "../include/fks_portable_math.h")]
+PLAN_HEADERS = ("csrc/fks_batch.h", "csrc/fks_device.h", "../include/fks_capi.h", "../include/fks_portable_math.h")
+SELECT_HEADERS = PLAN_HEADERS + ("csrc/fks_host_distance.h", "csrc/fks_se3.h")
+
+
+def _build_host_test(name: str, sources=(), headers=(), force: bool = False) -> str:
+    """Compile tests/cpp/<name>.cpp with the library's host-only units `sources` (paths under the
+    package): g++ with AddressSanitizer and UndefinedBehaviorSanitizer, no HIP runtime and no
+    libfks_hip.so (ROCm's include path only for the types its headers name).  Output: build/<name>."""
+    srcs = [os.path.join(ROOT, "tests", "cpp", name + ".cpp")] + [os.path.join(PKG, s) for s in sources]
+    deps = srcs + [os.path.join(PKG, h) for h in headers]
     out_dir = os.path.join(ROOT, "build")
     os.makedirs(out_dir, exist_ok=True)
-    target = os.path.join(out_dir, "batch_plan_test")
+    target = os.path.join(out_dir, name)
     if not force and os.path.exists(target) and all(os.path.getmtime(target) >= os.path.getmtime(p) for p in deps):
         return target
     rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "include")
@@ -219,53 +222,28 @@ def build_batch_plan_test(force: bool = False) -> str:
     if proc.returncode != 0:
         raise RuntimeError("g++ failed:\n" + proc.stdout[-6000:])
     return target
+
+
+def build_batch_plan_test(force: bool = False) -> str:
+    """tests/cpp/batch_plan_test.cpp with csrc/fks_batch.cpp, the host-only plan of batched calls."""
+    return _build_host_test("batch_plan_test", ("csrc/fks_batch.cpp",), PLAN_HEADERS, force)
 
 
 def build_policy_plan_test(force: bool = False) -> str:
-    """Compile tests/cpp/policy_plan_test.cpp with csrc/fks_batch.cpp and csrc/fks_policy_select.cpp, the
-    host-only plan of a policy roll-out and the host selection: g++ with AddressSanitizer and
-    UndefinedBehaviorSanitizer, no HIP runtime and no libfks_hip.so, as build_batch_plan_test."""
-    srcs = [os.path.join(ROOT, "tests", "cpp", "policy_plan_test.cpp"), os.path.join(PKG, "csrc", "fks_batch.cpp"),
-            os.path.join(PKG, "csrc", "fks_policy_select.cpp")]
-    deps = srcs + [os.path.join(PKG, h) for h in ("csrc/fks_batch.h", "csrc/fks_device.h", "csrc/fks_host_distance.h", "csrc/fks_se3.h",
-                                                  "../include/fks_capi.h", "../include/fks_portable_math.h")]
-    out_dir = os.path.join(ROOT, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    target = os.path.join(out_dir, "policy_plan_test")
-    if not force and os.path.exists(target) and all(os.path.getmtime(target) >= os.path.getmtime(p) for p in deps):
-        return target
-    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "include")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-D__HIP_PLATFORM_AMD__",
-           f"-I{os.path.join(ROOT, 'include')}", f"-I{os.path.join(PKG, 'csrc')}", f"-isystem{rocm_include}", *srcs, "-o", target]
-    proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if proc.returncode != 0:
-        raise RuntimeError("g++ failed:\n" + proc.stdout[-6000:])
-    return target
+    """tests/cpp/policy_plan_test.cpp with the host-only plan of a policy roll-out and the host selection."""
+    return _build_host_test("policy_plan_test", ("csrc/fks_batch.cpp", "csrc/fks_policy_select.cpp"), SELECT_HEADERS, force)
 
 
 def build_cluster_plan_test(force: bool = False) -> str:
-    """Compile tests/cpp/cluster_plan_test.cpp with csrc/fks_batch.cpp, csrc/fks_cluster.cpp and
-    csrc/fks_policy_select.cpp, the host-only plan of a clustering call and the host twin: g++ with
-    AddressSanitizer and UndefinedBehaviorSanitizer, no HIP runtime and no libfks_hip.so, as
-    build_policy_plan_test."""
-    srcs = [os.path.join(ROOT, "tests", "cpp", "cluster_plan_test.cpp"), os.path.join(PKG, "csrc", "fks_batch.cpp"),
-            os.path.join(PKG, "csrc", "fks_cluster.cpp"), os.path.join(PKG, "csrc", "fks_policy_select.cpp")]
-    deps = srcs + [os.path.join(PKG, h) for h in ("csrc/fks_batch.h", "csrc/fks_device.h", "csrc/fks_host_distance.h", "csrc/fks_se3.h",
-                                                  "../include/fks_capi.h", "../include/fks_portable_math.h")]
-    out_dir = os.path.join(ROOT, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    target = os.path.join(out_dir, "cluster_plan_test")
-    if not force and os.path.exists(target) and all(os.path.getmtime(target) >= os.path.getmtime(p) for p in deps):
-        return target
-    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "include")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-D__HIP_PLATFORM_AMD__",
-           f"-I{os.path.join(ROOT, 'include')}", f"-I{os.path.join(PKG, 'csrc')}", f"-isystem{rocm_include}", *srcs, "-o", target]
-    proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if proc.returncode != 0:
-        raise RuntimeError("g++ failed:\n" + proc.stdout[-6000:])
-    return target
+    """tests/cpp/cluster_plan_test.cpp with the host-only plan of a clustering call and the host twin."""
+    return _build_host_test("cluster_plan_test", ("csrc/fks_batch.cpp", "csrc/fks_cluster.cpp", "csrc/fks_policy_select.cpp"),
+                            SELECT_HEADERS, force)
+
+
+def build_buffers_test(force: bool = False) -> str:
+    """tests/cpp/buffers_test.cpp over csrc/fks_buffers.h alone: the program defines the four HIP
+    allocation calls itself, so that it can count the live blocks and fail a chosen allocation."""
+    return _build_host_test("buffers_test", (), ("csrc/fks_buffers.h",), force)
 
 
 def build_policy_test(force: bool = False, workspace: bool = False) -> str:

@@ -16,6 +16,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
@@ -23,6 +24,7 @@
 
 #include "fks_capi.h"
 #include "fks_batch.h"
+#include "fks_buffers.h"
 #include "fks_env_internal.h"
 #include "fks_specialize.h"
 #include "fks_device.h"
@@ -129,6 +131,8 @@ policy_kernel_t policy_kernel_of(bool small, int robot_type, bool lean) {
 }
 
 using fks_batch::splitmix64;
+using fks_buf::DeviceBuffer;
+using fks_buf::MirroredBuffer;
 
 using fksd::GridDev;
 /* a segment averaging this many resolver iterations per controller step is
@@ -177,6 +181,14 @@ hipError_t dev_upload(T** dptr, const T* host, size_t count) {
     hipError_t e = hipMalloc((void**)dptr, count * sizeof(T));
     if (e != hipSuccess) return e;
     return hipMemcpy(*dptr, host, count * sizeof(T), hipMemcpyHostToDevice);
+}
+
+/* `count` elements of `src` (host or device memory) in a block of `b`'s own */
+template <typename T>
+hipError_t upload(DeviceBuffer<T>& b, const T* src, size_t count, hipMemcpyKind kind = hipMemcpyHostToDevice) {
+    const hipError_t e = b.reserve(count);
+    if (e != hipSuccess) return e;
+    return hipMemcpy(b.get(), src, count * sizeof(T), kind);
 }
 
 bool valid_grid(const fks_grid_geometry& g) {
@@ -282,10 +294,10 @@ struct fks_context {
     uint64_t seed = 0;
     uint64_t call_index = 0;
     /* environment */
-    float* d_sdf = nullptr;     /* bricked (fks_device.h brick_cell) */
-    uint32_t* d_noff = nullptr; /* VoxelGrid-order CSR offsets, only until they are bricked */
-    uint2* d_nrange = nullptr;  /* bricked [begin, end) per normal-grid cell */
-    double* d_nent = nullptr;
+    DeviceBuffer<float> d_sdf;     /* bricked (fks_device.h brick_cell) */
+    DeviceBuffer<uint32_t> d_noff; /* VoxelGrid-order CSR offsets, only until they are bricked */
+    DeviceBuffer<uint2> d_nrange;  /* bricked [begin, end) per normal-grid cell */
+    DeviceBuffer<double> d_nent;
     GridDev sdf_g, nrm_g, env_g;
     float oob = 0.0f;
     int32_t has_normals = 0;
@@ -296,8 +308,7 @@ struct fks_context {
     RobotDev R;
     std::vector<void*> robot_allocs;
     /* launch resources */
-    double* d_scratch = nullptr;
-    size_t cap_scratch = 0; /* doubles allocated at d_scratch */
+    DeviceBuffer<double> d_scratch; /* the persistent grid's per-wave workspaces */
     uint64_t scratch_per_wave = 0;
     uint32_t grid_waves = 0;
     uint32_t waves_per_cu = 0;     /* resident waves per CU of the layout (LDS and registers) */
@@ -308,33 +319,25 @@ struct fks_context {
     uint32_t grid_groups = 0;
     uint32_t waves_per_group = fksd::kWavesPerGroup;
     size_t lds_bytes = 0;
-    unsigned long long* d_counters = nullptr; /* kNumCounters + queue + phase cycles */
+    MirroredBuffer<unsigned long long> counters; /* kNumCounters + queue + phase cycles, and their pinned copy */
     uint64_t phase_last[FKS_NUM_PHASES] = {};
     uint64_t phase_total[FKS_NUM_PHASES] = {};
-    unsigned long long* h_counters = nullptr; /* pinned */
-    fksd::SimArgs* d_args = nullptr;          /* kernel arguments, read through a pointer */
-    fksd::SimArgs* h_args = nullptr;          /* pinned staging for d_args */
-    uint32_t* d_policy_choice = nullptr; /* fks_forward_simulate_policy's host entry: the selection's staging */
-    double* d_policy_distance = nullptr;
-    uint32_t* d_policy_legs = nullptr;
-    double* d_policy_in = nullptr; /* and its inputs' own: the starts with the table behind them */
-    size_t cap_policy_sel = 0, cap_policy_in = 0;
+    MirroredBuffer<fksd::SimArgs> args; /* kernel arguments, read through a pointer, staged in pinned memory */
+    DeviceBuffer<uint32_t> d_policy_choice; /* fks_forward_simulate_policy's host entry: the selection's staging */
+    DeviceBuffer<double> d_policy_distance;
+    DeviceBuffer<uint32_t> d_policy_legs;
+    DeviceBuffer<double> d_policy_in; /* and its inputs' own: the starts with the table behind them */
     /* fks_cluster_configs_device: the staged offsets (pinned, then in HBM) and the HBM link workspace ... */
-    uint64_t* h_cluster_off = nullptr;
-    uint64_t* d_cluster_off = nullptr;
-    double* d_cluster_work = nullptr;
-    size_t cap_cluster_off = 0, cap_cluster_work = 0;
+    MirroredBuffer<uint64_t> cluster_off;
+    DeviceBuffer<double> d_cluster_work;
     /* ... and the host entry's staging: the configurations, the matrices, the labels and the counts */
-    double* d_cluster_in = nullptr;
-    double* d_cluster_mat = nullptr;
-    uint32_t* d_cluster_labels = nullptr;
-    uint32_t* d_cluster_counts = nullptr;
-    size_t cap_cluster_in = 0, cap_cluster_mat = 0, cap_cluster_labels = 0, cap_cluster_counts = 0;
-    fksd::SimArgs* d_path_args = nullptr;     /* a batch's records (fks_batch::build_records): one per (job, leg) of
-                                                 its normal form (a path's legs, a job batch's jobs), then job_first
-                                                 and leg_first (SimArgs.job_first) */
-    fksd::SimArgs* h_path_args = nullptr;     /* pinned staging for d_path_args */
-    size_t cap_path_args = 0;
+    DeviceBuffer<double> d_cluster_in;
+    DeviceBuffer<double> d_cluster_mat;
+    DeviceBuffer<uint32_t> d_cluster_labels;
+    DeviceBuffer<uint32_t> d_cluster_counts;
+    MirroredBuffer<fksd::SimArgs> path_args; /* a batch's records (fks_batch::build_records): one per (job, leg) of
+                                                its normal form (a path's legs, a job batch's jobs), then job_first
+                                                and leg_first (SimArgs.job_first) */
     std::vector<unsigned char> jobs_stage;    /* fks_forward_simulate_jobs / _path_jobs: the jobs' inputs, then outputs, end to end */
     bool pending = false;
     int pending_kind = 0; /* 0 = forward simulation, 1 = batched config check, 2 = clustering (nothing to fold) */
@@ -342,16 +345,8 @@ struct fks_context {
     fks_call_counters check_last;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::chrono::steady_clock::time_point call_start;
-    /* host-API staging */
-    double* d_starts = nullptr;
-    double* d_targets = nullptr;
-    double* d_out = nullptr;
-    uint8_t* d_coll = nullptr;
-    uint32_t* d_micro = nullptr;
-    uint32_t* d_res = nullptr;
-    uint32_t* d_err = nullptr;
-    double* d_pid = nullptr; /* fks_forward_simulate_mutable controller state */
-    size_t cap_particles = 0, cap_targets = 0, cap_pid = 0;
+    fks_buf::ParticleStaging stage; /* host-API staging */
+    DeviceBuffer<double> d_pid;     /* fks_forward_simulate_mutable controller state */
     /* controller-step segments: resting particle state between segments */
     uint32_t segment_steps = 0; /* 0 = automatic (kDefaultSegmentSteps) */
     uint32_t heavy_per_step = kHeavyResolverPerStep; /* fks_set_segment_policy */
@@ -365,9 +360,8 @@ struct fks_context {
     uint32_t standard_resident_waves = 0; /* resident waves of the non-lean layout (fks_get_launch_info) */
     int32_t last_kernel = FKS_KERNEL_NONE;       /* the simulation kernel of the last call */
     int32_t last_check_kernel = FKS_KERNEL_NONE; /* the configuration-check kernel of the last check */
-    double* d_seg_state = nullptr;
-    uint32_t* d_seg_done = nullptr;
-    size_t cap_seg_state = 0, cap_seg_done = 0;
+    DeviceBuffer<double> d_seg_state;
+    DeviceBuffer<uint32_t> d_seg_done;
     fks_statistics stats;
     fks_call_counters last;
     fks_call_counters total;
@@ -379,13 +373,6 @@ struct fks_context {
     int32_t bspec_enabled = 0; /* opt-in: fks_set_batched_specialization / fks_prepare_batched_specialization */
     ShapedModule bspec;        /* fks_simulate_shaped_pj[_small] */
 };
-
-template <typename T>
-static hipError_t ensure(T** p, size_t count) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    return hipMalloc((void**)p, (count > 0 ? count : 1) * sizeof(T));
-}
 
 static fks_status fail(fks_context* ctx, fks_status st, const std::string& msg) {
     if (ctx) ctx->last_error = msg;
@@ -408,28 +395,8 @@ static void free_robot(fks_context* ctx) {
     ctx->bspec.pending = false;
     for (void* p : ctx->robot_allocs) (void)hipFree(p);
     ctx->robot_allocs.clear();
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    ctx->d_scratch = nullptr;
-    ctx->cap_scratch = 0;
+    ctx->d_scratch.reset();
     ctx->has_robot = false;
-}
-
-static void free_staging(fks_context* ctx) {
-    void* ptrs[] = {ctx->d_starts, ctx->d_targets, ctx->d_out, ctx->d_coll, ctx->d_micro, ctx->d_res, ctx->d_err};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    ctx->d_starts = ctx->d_targets = ctx->d_out = nullptr;
-    ctx->d_coll = nullptr;
-    ctx->d_micro = ctx->d_res = ctx->d_err = nullptr;
-    ctx->cap_particles = ctx->cap_targets = 0;
-    if (ctx->d_pid) (void)hipFree(ctx->d_pid);
-    ctx->d_pid = nullptr;
-    ctx->cap_pid = 0;
-    if (ctx->d_seg_state) (void)hipFree(ctx->d_seg_state);
-    if (ctx->d_seg_done) (void)hipFree(ctx->d_seg_done);
-    ctx->d_seg_state = nullptr;
-    ctx->d_seg_done = nullptr;
-    ctx->cap_seg_state = ctx->cap_seg_done = 0;
 }
 
 /* unloads a module and clears its report; `pending` is the caller's to set */
@@ -644,7 +611,8 @@ static fks_status create_impl(const fks_environment* henv, const fks_device_env*
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return FKS_ERR_NO_DEVICE;
     if (device < 0 || device >= count) return FKS_ERR_INVALID_ARGUMENT;
-    fks_context* ctx = new (std::nothrow) fks_context();
+    /* destroyed with whatever it owns by then on every early return */
+    std::unique_ptr<fks_context, void (*)(fks_context*)> ctx(new (std::nothrow) fks_context(), fks_destroy);
     if (!ctx) return FKS_ERR_OUT_OF_MEMORY;
     ctx->device = device;
     ctx->params = *params;
@@ -658,14 +626,7 @@ static fks_status create_impl(const fks_environment* henv, const fks_device_env*
     std::memset(&ctx->stats, 0, sizeof(ctx->stats));
     std::memset(&ctx->last, 0, sizeof(ctx->last));
     std::memset(&ctx->total, 0, sizeof(ctx->total));
-    auto bail = [&](hipError_t e, const char* where) {
-        (void)where;
-        (void)e;
-        fks_destroy(ctx);
-        return FKS_ERR_HIP;
-    };
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return bail(e, "hipSetDevice");
+    if (hipSetDevice(device) != hipSuccess) return FKS_ERR_HIP;
     double lp = 0.0, cm = 0.0;
     bool analyzed = false;
     if (henv) {
@@ -674,7 +635,7 @@ static fks_status create_impl(const fks_environment* henv, const fks_device_env*
         ctx->env_g = make_grid(henv->collision_map);
         ctx->oob = henv->sdf_oob_value;
         const size_t cells = (size_t)henv->sdf.num_cells[0] * (size_t)henv->sdf.num_cells[1] * (size_t)henv->sdf.num_cells[2];
-        if ((e = dev_upload(&ctx->d_sdf, henv->sdf_values, cells)) != hipSuccess) return bail(e, "sdf upload");
+        if (upload(ctx->d_sdf, henv->sdf_values, cells) != hipSuccess) return FKS_ERR_HIP;
         analyzed = analyze_sdf(henv->sdf_values, henv->sdf.num_cells[0], henv->sdf.num_cells[1], henv->sdf.num_cells[2],
                                henv->sdf.resolution, &lp, &cm);
         /* an initialized grid with no stored entries (every cell empty: a lookup in bounds finds
@@ -683,14 +644,9 @@ static fks_status create_impl(const fks_environment* henv, const fks_device_env*
             const size_t ncells =
                 (size_t)henv->normals.num_cells[0] * (size_t)henv->normals.num_cells[1] * (size_t)henv->normals.num_cells[2];
             const size_t entries = henv->normal_offsets[ncells];
-            if (entries > 0 && !henv->normal_entries) {
-                fks_destroy(ctx);
-                return FKS_ERR_INVALID_ARGUMENT;
-            }
-            if ((e = dev_upload(&ctx->d_noff, henv->normal_offsets, ncells + 1)) != hipSuccess)
-                return bail(e, "normal offsets upload");
-            if (entries > 0 && (e = dev_upload(&ctx->d_nent, henv->normal_entries, 6 * entries)) != hipSuccess)
-                return bail(e, "normal entries upload");
+            if (entries > 0 && !henv->normal_entries) return FKS_ERR_INVALID_ARGUMENT;
+            if (upload(ctx->d_noff, henv->normal_offsets, ncells + 1) != hipSuccess) return FKS_ERR_HIP;
+            if (entries > 0 && upload(ctx->d_nent, henv->normal_entries, 6 * entries) != hipSuccess) return FKS_ERR_HIP;
             ctx->has_normals = 1;
         }
     } else {
@@ -700,20 +656,13 @@ static fks_status create_impl(const fks_environment* henv, const fks_device_env*
         ctx->env_g = ctx->sdf_g;
         ctx->oob = std::numeric_limits<float>::infinity();
         const size_t cells = (size_t)denv->cells;
-        if ((e = hipMalloc((void**)&ctx->d_sdf, cells * sizeof(float))) != hipSuccess) return bail(e, "sdf");
-        if ((e = hipMemcpy(ctx->d_sdf, denv->sdf, cells * sizeof(float), hipMemcpyDeviceToDevice)) != hipSuccess)
-            return bail(e, "sdf copy");
-        analyzed = fks_env::analyze_sdf_device(ctx->d_sdf, denv->geometry.num_cells[0], denv->geometry.num_cells[1],
+        if (upload(ctx->d_sdf, denv->sdf, cells, hipMemcpyDeviceToDevice) != hipSuccess) return FKS_ERR_HIP;
+        analyzed = fks_env::analyze_sdf_device(ctx->d_sdf.get(), denv->geometry.num_cells[0], denv->geometry.num_cells[1],
                                                denv->geometry.num_cells[2], denv->geometry.resolution, &lp, &cm);
-        if ((e = hipMalloc((void**)&ctx->d_noff, (cells + 1) * sizeof(uint32_t))) != hipSuccess) return bail(e, "offsets");
-        if ((e = hipMemcpy(ctx->d_noff, denv->offsets, (cells + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice)) != hipSuccess)
-            return bail(e, "offsets copy");
-        if (denv->num_entries > 0) {
-            const size_t bytes = 6 * (size_t)denv->num_entries * sizeof(double);
-            if ((e = hipMalloc((void**)&ctx->d_nent, bytes)) != hipSuccess) return bail(e, "entries");
-            if ((e = hipMemcpy(ctx->d_nent, denv->entries, bytes, hipMemcpyDeviceToDevice)) != hipSuccess)
-                return bail(e, "entries copy");
-        }
+        if (upload(ctx->d_noff, denv->offsets, cells + 1, hipMemcpyDeviceToDevice) != hipSuccess) return FKS_ERR_HIP;
+        if (denv->num_entries > 0 &&
+            upload(ctx->d_nent, denv->entries, 6 * (size_t)denv->num_entries, hipMemcpyDeviceToDevice) != hipSuccess)
+            return FKS_ERR_HIP;
         ctx->has_normals = 1;
     }
     if (analyzed) {
@@ -724,28 +673,24 @@ static fks_status create_impl(const fks_environment* henv, const fks_device_env*
     /* the kernels' HBM layout: the SDF and the normal ranges in 4x4x4-cell bricks (the
      * analysis above read the VoxelGrid order) */
     {
+        /* the bricking allocates its output (none on a failure), which replaces its input */
         float* bricked = nullptr;
-        if ((e = fks_env::brick_sdf_device(ctx->d_sdf, ctx->sdf_g.n, ctx->sdf_g.nb, &bricked)) != hipSuccess)
-            return bail(e, "sdf bricks");
-        (void)hipFree(ctx->d_sdf);
-        ctx->d_sdf = bricked;
-        if (ctx->d_noff) {
-            if ((e = fks_env::brick_normal_ranges_device(ctx->d_noff, ctx->nrm_g.n, ctx->nrm_g.nb, &ctx->d_nrange)) != hipSuccess)
-                return bail(e, "normal-range bricks");
-            (void)hipFree(ctx->d_noff);
-            ctx->d_noff = nullptr;
+        if (fks_env::brick_sdf_device(ctx->d_sdf.get(), ctx->sdf_g.n, ctx->sdf_g.nb, &bricked) != hipSuccess) return FKS_ERR_HIP;
+        ctx->d_sdf.adopt(bricked, (size_t)fksd::brick_total(ctx->sdf_g.nb));
+        if (ctx->d_noff.get()) {
+            uint2* ranges = nullptr;
+            if (fks_env::brick_normal_ranges_device(ctx->d_noff.get(), ctx->nrm_g.n, ctx->nrm_g.nb, &ranges) != hipSuccess)
+                return FKS_ERR_HIP;
+            ctx->d_nrange.adopt(ranges, (size_t)fksd::brick_total(ctx->nrm_g.nb));
+            ctx->d_noff.reset();
         }
     }
-    if ((e = hipMalloc((void**)&ctx->d_counters, fksd::kCounterWords * sizeof(unsigned long long))) != hipSuccess)
-        return bail(e, "counters");
-    if ((e = hipHostMalloc((void**)&ctx->h_counters, fksd::kCounterWords * sizeof(unsigned long long), 0)) != hipSuccess)
-        return bail(e, "pinned counters");
-    if ((e = hipMalloc((void**)&ctx->d_args, sizeof(fksd::SimArgs))) != hipSuccess) return bail(e, "kernel arguments");
-    if ((e = hipHostMalloc((void**)&ctx->h_args, sizeof(fksd::SimArgs), 0)) != hipSuccess) return bail(e, "kernel arguments");
-    if ((e = hipEventCreate(&ctx->ev0)) != hipSuccess) return bail(e, "event");
-    if ((e = hipEventCreate(&ctx->ev1)) != hipSuccess) return bail(e, "event");
+    if (ctx->counters.reserve(fksd::kCounterWords) != hipSuccess) return FKS_ERR_HIP;
+    if (ctx->args.reserve(1) != hipSuccess) return FKS_ERR_HIP;
+    if (hipEventCreate(&ctx->ev0) != hipSuccess) return FKS_ERR_HIP;
+    if (hipEventCreate(&ctx->ev1) != hipSuccess) return FKS_ERR_HIP;
     (void)same_geometry;
-    *out_ctx = ctx;
+    *out_ctx = ctx.release();
     return FKS_OK;
 }
 
@@ -770,31 +715,9 @@ void fks_destroy(fks_context* ctx) {
     shaped_release(ctx, &ctx->spec);
     shaped_release(ctx, &ctx->bspec);
     free_robot(ctx);
-    free_staging(ctx);
-    if (ctx->d_sdf) (void)hipFree(ctx->d_sdf);
-    if (ctx->d_noff) (void)hipFree(ctx->d_noff);
-    if (ctx->d_nrange) (void)hipFree(ctx->d_nrange);
-    if (ctx->d_nent) (void)hipFree(ctx->d_nent);
-    if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-    if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
-    if (ctx->d_args) (void)hipFree(ctx->d_args);
-    if (ctx->h_args) (void)hipHostFree(ctx->h_args);
-    if (ctx->d_path_args) (void)hipFree(ctx->d_path_args);
-    if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
-    if (ctx->d_policy_choice) (void)hipFree(ctx->d_policy_choice);
-    if (ctx->d_policy_distance) (void)hipFree(ctx->d_policy_distance);
-    if (ctx->d_policy_legs) (void)hipFree(ctx->d_policy_legs);
-    if (ctx->d_policy_in) (void)hipFree(ctx->d_policy_in);
-    if (ctx->h_cluster_off) (void)hipHostFree(ctx->h_cluster_off);
-    if (ctx->d_cluster_off) (void)hipFree(ctx->d_cluster_off);
-    if (ctx->d_cluster_work) (void)hipFree(ctx->d_cluster_work);
-    if (ctx->d_cluster_in) (void)hipFree(ctx->d_cluster_in);
-    if (ctx->d_cluster_mat) (void)hipFree(ctx->d_cluster_mat);
-    if (ctx->d_cluster_labels) (void)hipFree(ctx->d_cluster_labels);
-    if (ctx->d_cluster_counts) (void)hipFree(ctx->d_cluster_counts);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    delete ctx;
+    delete ctx; /* every buffer goes with its owner, on the device selected above */
 }
 
 const char* fks_get_last_error(const fks_context* ctx) { return ctx ? ctx->last_error.c_str() : "null context"; }
@@ -879,18 +802,12 @@ static fks_status launch_layout(fks_context* ctx, const fksd::RobotDev& R) {
      * as half the free HBM holds (the ticket queue hands out the work either way) */
     size_t free_b = 0, total_b = 0;
     HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-    free_b += ctx->cap_scratch * sizeof(double); /* the current workspace is given back below */
+    free_b += ctx->d_scratch.capacity() * sizeof(double); /* the current workspace is given back below */
     const size_t per_group = (size_t)wpg * scratch_per_wave * sizeof(double);
     const size_t max_groups = std::max<size_t>(1, (free_b / 2) / std::max<size_t>(1, per_group));
     if ((size_t)grid_groups > max_groups) grid_groups = (uint32_t)max_groups;
     const size_t words = (size_t)grid_groups * wpg * scratch_per_wave;
-    if (words > ctx->cap_scratch || !ctx->d_scratch) {
-        if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-        ctx->d_scratch = nullptr;
-        ctx->cap_scratch = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_scratch, words * sizeof(double)));
-        ctx->cap_scratch = words;
-    }
+    HIP_TRY(ctx, ctx->d_scratch.reserve(words)); /* frees the current workspace before it allocates a larger one */
     ctx->fk_pair = pair;
     ctx->lean = lean;
     ctx->standard_resident_waves = (uint32_t)(cus * std::max(0, standard_waves_per_cu));
@@ -1300,7 +1217,7 @@ static fks_status settle(fks_context* ctx) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->pending_stream));
     ctx->pending = false;
     if (ctx->pending_kind == 2) return FKS_OK; /* a clustering call: no counters, no statistics */
-    const unsigned long long* c = ctx->h_counters;
+    const unsigned long long* c = ctx->counters.host();
     if (ctx->pending_kind == 1) {
         /* a config check: no simulator statistics, only its own counters */
         float ms = 0.0f;
@@ -1389,9 +1306,9 @@ static void plan_inputs(const fks_context* ctx, fks_batch::Inputs* in) {
     a.sdf_g = ctx->sdf_g;
     a.nrm_g = ctx->nrm_g;
     a.env_g = ctx->env_g;
-    a.sdf = ctx->d_sdf;
-    a.nrange = ctx->d_nrange;
-    a.nent = ctx->d_nent;
+    a.sdf = ctx->d_sdf.get();
+    a.nrange = ctx->d_nrange.get();
+    a.nent = ctx->d_nent.get();
     a.oob = ctx->oob;
     a.has_normals = ctx->has_normals;
     a.skip_enabled = ctx->skip_enabled;
@@ -1406,9 +1323,9 @@ static void plan_inputs(const fks_context* ctx, fks_batch::Inputs* in) {
     a.time_multiplier = 1.0 / a.dt;
     a.T = in->T;
     a.individual_jacobians = ctx->individual_jacobians;
-    a.counters = ctx->d_counters;
-    a.queue = ctx->d_counters + fksd::kNumCounters;
-    a.scratch = ctx->d_scratch;
+    a.counters = ctx->counters.dev();
+    a.queue = ctx->counters.dev() + fksd::kNumCounters;
+    a.scratch = ctx->d_scratch.get();
     a.scratch_per_wave = ctx->scratch_per_wave;
     a.row_cap = 3u * (uint32_t)ctx->R.P;
     a.L = fksd::make_lds_layout(ctx->R.L, ctx->R.J, ctx->R.D, ctx->R.W, ctx->R.G, ctx->R.nrounds, ctx->fk_pair, ctx->lean);
@@ -1547,36 +1464,24 @@ static fks_status simulate_device(fks_context* ctx, const SimRequest& rq) {
     double* seg_state = nullptr;
     uint32_t* seg_done = nullptr;
     if (plan.seg_state_words) {
-        if (plan.seg_state_words > ctx->cap_seg_state) {
-            HIP_TRY(ctx, ensure(&ctx->d_seg_state, (size_t)plan.seg_state_words));
-            ctx->cap_seg_state = (size_t)plan.seg_state_words;
-        }
-        seg_state = ctx->d_seg_state;
+        HIP_TRY(ctx, ctx->d_seg_state.reserve((size_t)plan.seg_state_words));
+        seg_state = ctx->d_seg_state.get();
     }
     if (plan.seg_done_words) {
-        if (plan.seg_done_words > ctx->cap_seg_done) {
-            HIP_TRY(ctx, ensure(&ctx->d_seg_done, (size_t)plan.seg_done_words));
-            ctx->cap_seg_done = (size_t)plan.seg_done_words;
-        }
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_seg_done, 0, (size_t)plan.seg_done_words * sizeof(uint32_t), s));
-        seg_done = ctx->d_seg_done;
+        HIP_TRY(ctx, ctx->d_seg_done.reserve((size_t)plan.seg_done_words));
+        seg_done = ctx->d_seg_done.get();
+        HIP_TRY(ctx, hipMemsetAsync(seg_done, 0, (size_t)plan.seg_done_words * sizeof(uint32_t), s));
     }
-    const fksd::SimArgs* d_launch_args = ctx->d_args;
+    const fksd::SimArgs* d_launch_args = ctx->args.dev();
     if (batch) {
         /* the previous call has settled, so the pinned staging copies are free */
-        if (records.records > ctx->cap_path_args) {
-            if (ctx->h_path_args) (void)hipHostFree(ctx->h_path_args);
-            ctx->h_path_args = nullptr;
-            ctx->cap_path_args = 0;
-            HIP_TRY(ctx, ensure(&ctx->d_path_args, records.records));
-            HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_path_args, records.records * sizeof(fksd::SimArgs), 0));
-            ctx->cap_path_args = records.records;
-        }
-        fks_batch::build_records(in, *batch, seg_state, seg_done, ctx->d_path_args, ctx->h_path_args);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path_args, ctx->h_path_args, records.records * sizeof(fksd::SimArgs), hipMemcpyHostToDevice, s));
-        d_launch_args = ctx->d_path_args;
+        HIP_TRY(ctx, ctx->path_args.reserve(records.records));
+        fks_batch::build_records(in, *batch, seg_state, seg_done, ctx->path_args.dev(), ctx->path_args.host());
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->path_args.dev(), ctx->path_args.host(), records.records * sizeof(fksd::SimArgs),
+                                    hipMemcpyHostToDevice, s));
+        d_launch_args = ctx->path_args.dev();
     } else {
-        fksd::SimArgs& a = *ctx->h_args;
+        fksd::SimArgs& a = *ctx->args.host();
         a = in.base;
         const uint64_t key = splitmix64(in.seed ^ splitmix64(in.call_index));
         a.key0 = (uint32_t)key;
@@ -1606,9 +1511,9 @@ static fks_status simulate_device(fks_context* ctx, const SimRequest& rq) {
             a.tr_step_cap = tr->step_cap;
             a.tr_cfg_cap = tr->cfg_cap;
         }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_args, ctx->h_args, sizeof(a), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->args.dev(), ctx->args.host(), sizeof(a), hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, fksd::kCounterWords * sizeof(unsigned long long), s));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.dev(), 0, fksd::kCounterWords * sizeof(unsigned long long), s));
     const uint64_t groups_needed = (n + ctx->waves_per_group - 1) / ctx->waves_per_group;
     const uint32_t grid = (uint32_t)((groups_needed < (uint64_t)ctx->grid_groups) ? (groups_needed > 0 ? groups_needed : 1)
                                                                                   : ctx->grid_groups);
@@ -1622,7 +1527,7 @@ static fks_status simulate_device(fks_context* ctx, const SimRequest& rq) {
                                            nullptr));
         l.module->launches++;
     } else if (l.policy) {
-        const fksd::PolicyArgs* pol = reinterpret_cast<const fksd::PolicyArgs*>(ctx->d_path_args + records.policy_record);
+        const fksd::PolicyArgs* pol = reinterpret_cast<const fksd::PolicyArgs*>(ctx->path_args.dev() + records.policy_record);
         hipLaunchKernelGGL(l.policy, dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args, pol);
     } else if (l.coop) {
         hipLaunchKernelGGL(l.kernel, dim3((uint32_t)n), dim3(64 * ctx->coop_waves), ctx->coop_lds_bytes, s, d_launch_args);
@@ -1631,7 +1536,7 @@ static fks_status simulate_device(fks_context* ctx, const SimRequest& rq) {
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, fksd::kCounterWords * sizeof(unsigned long long),
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->counters.host(), ctx->counters.dev(), fksd::kCounterWords * sizeof(unsigned long long),
                                 hipMemcpyDeviceToHost, s));
     ctx->pending = true;
     ctx->pending_kind = 0;
@@ -1675,9 +1580,9 @@ fks_status fks_check_config_collision_device(fks_context* ctx, const double* d_c
     a.sdf_g = ctx->sdf_g;
     a.nrm_g = ctx->nrm_g;
     a.env_g = ctx->env_g;
-    a.sdf = ctx->d_sdf;
-    a.nrange = ctx->d_nrange;
-    a.nent = ctx->d_nent;
+    a.sdf = ctx->d_sdf.get();
+    a.nrange = ctx->d_nrange.get();
+    a.nent = ctx->d_nent.get();
     a.oob = ctx->oob;
     a.has_normals = ctx->has_normals;
     a.R = ctx->R;
@@ -1689,16 +1594,16 @@ fks_status fks_check_config_collision_device(fks_context* ctx, const double* d_c
     a.n = n;
     a.out_collided = d_out_collided;
     a.out_err = d_out_error_flags;
-    a.counters = ctx->d_counters;
-    a.queue = ctx->d_counters + fksd::kNumCounters;
-    a.scratch = ctx->d_scratch;
+    a.counters = ctx->counters.dev();
+    a.queue = ctx->counters.dev() + fksd::kNumCounters;
+    a.scratch = ctx->d_scratch.get();
     a.scratch_per_wave = ctx->scratch_per_wave;
     a.row_cap = 3u * (uint32_t)ctx->R.P;
     a.L = fksd::make_lds_layout(ctx->R.L, ctx->R.J, ctx->R.D, ctx->R.W, ctx->R.G, ctx->R.nrounds, ctx->fk_pair, ctx->lean);
     a.SL = fksd::make_scratch_layout(a.row_cap, ctx->R.D, ctx->R.P, ctx->R.G);
-    *ctx->h_args = a;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_args, ctx->h_args, sizeof(a), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, fksd::kCounterWords * sizeof(unsigned long long), s));
+    *ctx->args.host() = a;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->args.dev(), ctx->args.host(), sizeof(a), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.dev(), 0, fksd::kCounterWords * sizeof(unsigned long long), s));
     const uint64_t groups_needed = (n + ctx->waves_per_group - 1) / ctx->waves_per_group;
     const uint32_t grid = (uint32_t)((groups_needed < (uint64_t)ctx->grid_groups) ? groups_needed : ctx->grid_groups);
     /* a batch larger than the resident grid runs the robot's shape-specialised check (built
@@ -1706,19 +1611,19 @@ fks_status fks_check_config_collision_device(fks_context* ctx, const double* d_c
     if (ctx->spec.pending && n > (uint64_t)ctx->grid_waves) shaped_build_pending(ctx, &ctx->spec, kPlainModule);
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
     if (ctx->spec.check_fn) {
-        const fksd::SimArgs* argp = ctx->d_args;
+        const fksd::SimArgs* argp = ctx->args.dev();
         void* params[] = {&argp};
         HIP_TRY(ctx, hipModuleLaunchKernel(ctx->spec.check_fn, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes,
                                            s, params, nullptr));
         ctx->last_check_kernel = FKS_KERNEL_SHAPED;
     } else {
         hipLaunchKernelGGL(kernel_of(KF_CHECK, false, ctx->R.type), dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s,
-                           static_cast<const fksd::SimArgs*>(ctx->d_args));
+                           static_cast<const fksd::SimArgs*>(ctx->args.dev()));
         ctx->last_check_kernel = FKS_KERNEL_THROUGHPUT;
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, fksd::kCounterWords * sizeof(unsigned long long),
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->counters.host(), ctx->counters.dev(), fksd::kCounterWords * sizeof(unsigned long long),
                                 hipMemcpyDeviceToHost, s));
     ctx->pending = true;
     ctx->pending_kind = 1;
@@ -1736,21 +1641,13 @@ fks_status fks_check_config_collision(fks_context* ctx, const double* configs, u
     fks_status st = settle(ctx);
     if (st != FKS_OK) return st;
     const size_t W = (size_t)ctx->R.W;
-    if (n > ctx->cap_particles) {
-        HIP_TRY(ctx, ensure(&ctx->d_starts, n * W));
-        HIP_TRY(ctx, ensure(&ctx->d_out, n * W));
-        HIP_TRY(ctx, ensure(&ctx->d_coll, n));
-        HIP_TRY(ctx, ensure(&ctx->d_micro, n));
-        HIP_TRY(ctx, ensure(&ctx->d_res, n));
-        HIP_TRY(ctx, ensure(&ctx->d_err, n));
-        ctx->cap_particles = n;
-    }
+    fks_buf::ParticleStaging& sg = ctx->stage;
+    HIP_TRY(ctx, sg.reserve_rows(n, W));
     if (n == 0) return fks_check_config_collision_device(ctx, nullptr, 0, inflation_ratio, nullptr, nullptr, nullptr, 1);
-    HIP_TRY(ctx, hipMemcpy(ctx->d_starts, configs, n * W * sizeof(double), hipMemcpyHostToDevice));
-    st = fks_check_config_collision_device(ctx, ctx->d_starts, n, inflation_ratio, ctx->d_coll, ctx->d_err, nullptr, 1);
+    HIP_TRY(ctx, hipMemcpy(sg.starts.get(), configs, n * W * sizeof(double), hipMemcpyHostToDevice));
+    st = fks_check_config_collision_device(ctx, sg.starts.get(), n, inflation_ratio, sg.coll.get(), sg.err.get(), nullptr, 1);
     if (st != FKS_OK) return st;
-    HIP_TRY(ctx, hipMemcpy(out_collided, ctx->d_coll, n, hipMemcpyDeviceToHost));
-    if (out_error_flags) HIP_TRY(ctx, hipMemcpy(out_error_flags, ctx->d_err, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, sg.download(n, W, nullptr, out_collided, nullptr, nullptr, out_error_flags));
     ctx->check_last.call_ms =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
     return FKS_OK;
@@ -1777,50 +1674,32 @@ static fks_status simulate_host(fks_context* ctx, const double* starts, uint64_t
     fks_status st = settle(ctx);
     if (st != FKS_OK) return st;
     const size_t W = (size_t)ctx->R.W;
-    if (n > ctx->cap_particles) {
-        HIP_TRY(ctx, ensure(&ctx->d_starts, n * W));
-        HIP_TRY(ctx, ensure(&ctx->d_out, n * W));
-        HIP_TRY(ctx, ensure(&ctx->d_coll, n));
-        HIP_TRY(ctx, ensure(&ctx->d_micro, n));
-        HIP_TRY(ctx, ensure(&ctx->d_res, n));
-        HIP_TRY(ctx, ensure(&ctx->d_err, n));
-        ctx->cap_particles = n;
-    }
+    fks_buf::ParticleStaging& sg = ctx->stage;
+    HIP_TRY(ctx, sg.reserve_rows(n, W));
     const uint64_t nt = (n > 0) ? num_targets : 0;
-    if (nt > ctx->cap_targets || !ctx->d_targets) {
-        HIP_TRY(ctx, ensure(&ctx->d_targets, (nt > 0 ? nt : 1) * W));
-        ctx->cap_targets = nt > 0 ? nt : 1;
-    }
+    HIP_TRY(ctx, sg.reserve_targets(nt > 0 ? nt : 1, W)); /* one configuration also when there is no particle */
     if (n == 0) {
         ctx->call_index++;
         std::memset(&ctx->last, 0, sizeof(ctx->last));
         return FKS_OK;
     }
-    HIP_TRY(ctx, hipMemcpy(ctx->d_starts, starts, n * W * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_targets, targets, nt * W * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(sg.starts.get(), starts, n * W * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(sg.targets.get(), targets, nt * W * sizeof(double), hipMemcpyHostToDevice));
     const size_t pid_words = (size_t)n * 2u * (size_t)ctx->R.D;
     if (controller_state) {
-        if (pid_words > ctx->cap_pid) {
-            HIP_TRY(ctx, ensure(&ctx->d_pid, pid_words));
-            ctx->cap_pid = pid_words;
-        }
-        HIP_TRY(ctx, hipMemcpy(ctx->d_pid, controller_state, pid_words * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, ctx->d_pid.reserve(pid_words));
+        HIP_TRY(ctx, hipMemcpy(ctx->d_pid.get(), controller_state, pid_words * sizeof(double), hipMemcpyHostToDevice));
     }
     SimRequest rq;
-    rq.plain = plain_call(ctx->d_starts, n, ctx->d_targets, nt, 0, allow_contacts, ctx->d_out, ctx->d_coll, ctx->d_micro, ctx->d_res,
-                          ctx->d_err);
+    rq.plain = plain_call(sg.starts.get(), n, sg.targets.get(), nt, 0, allow_contacts, sg.out.get(), sg.coll.get(), sg.micro.get(),
+                          sg.res.get(), sg.err.get());
     rq.trace = tr;
-    rq.d_pid_io = controller_state ? ctx->d_pid : nullptr;
+    rq.d_pid_io = controller_state ? ctx->d_pid.get() : nullptr;
     st = simulate_device(ctx, rq);
     if (st != FKS_OK) return st;
     if (controller_state)
-        HIP_TRY(ctx, hipMemcpy(controller_state, ctx->d_pid, pid_words * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out_positions, ctx->d_out, n * W * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_collided) HIP_TRY(ctx, hipMemcpy(out_collided, ctx->d_coll, n, hipMemcpyDeviceToHost));
-    if (out_microsteps) HIP_TRY(ctx, hipMemcpy(out_microsteps, ctx->d_micro, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_resolver_iterations)
-        HIP_TRY(ctx, hipMemcpy(out_resolver_iterations, ctx->d_res, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_error_flags) HIP_TRY(ctx, hipMemcpy(out_error_flags, ctx->d_err, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(controller_state, ctx->d_pid.get(), pid_words * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, sg.download(n, W, out_positions, out_collided, out_microsteps, out_resolver_iterations, out_error_flags));
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
     return FKS_OK;
 }
@@ -1908,37 +1787,18 @@ fks_status fks_forward_simulate_path(fks_context* ctx, const double* starts, uin
     /* the staging buffers of the plain host calls, sized for the leg-major outputs */
     const size_t W = (size_t)ctx->R.W;
     const uint64_t rows = n * num_legs, nt = num_targets * num_legs;
-    if (rows > ctx->cap_particles) {
-        HIP_TRY(ctx, ensure(&ctx->d_starts, rows * W));
-        HIP_TRY(ctx, ensure(&ctx->d_out, rows * W));
-        HIP_TRY(ctx, ensure(&ctx->d_coll, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_micro, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_res, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_err, rows));
-        ctx->cap_particles = rows;
-    }
-    if (nt > ctx->cap_targets || !ctx->d_targets) {
-        HIP_TRY(ctx, ensure(&ctx->d_targets, nt * W));
-        ctx->cap_targets = nt;
-    }
-    HIP_TRY(ctx, hipMemcpy(ctx->d_starts, starts, n * W * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_targets, waypoints, nt * W * sizeof(double), hipMemcpyHostToDevice));
+    fks_buf::ParticleStaging& sg = ctx->stage;
+    HIP_TRY(ctx, sg.reserve_rows(rows, W));
+    HIP_TRY(ctx, sg.reserve_targets(nt, W));
+    HIP_TRY(ctx, hipMemcpy(sg.starts.get(), starts, n * W * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(sg.targets.get(), waypoints, nt * W * sizeof(double), hipMemcpyHostToDevice));
     fks_path_job& dev = b.converted[0]; /* the same path over the staging buffers */
-    dev.starts = ctx->d_starts;
-    dev.waypoints = ctx->d_targets;
-    dev.out_positions = ctx->d_out;
-    dev.out_collided = ctx->d_coll;
-    dev.out_microsteps = ctx->d_micro;
-    dev.out_resolver_iterations = ctx->d_res;
-    dev.out_error_flags = ctx->d_err;
+    dev.starts = sg.starts.get();
+    dev.waypoints = sg.targets.get();
+    sg.stage_outputs(&dev, 0, W);
     st = run_batch(ctx, in, b, nullptr, 1);
     if (st != FKS_OK) return st;
-    HIP_TRY(ctx, hipMemcpy(out_positions, ctx->d_out, rows * W * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_collided) HIP_TRY(ctx, hipMemcpy(out_collided, ctx->d_coll, rows, hipMemcpyDeviceToHost));
-    if (out_microsteps) HIP_TRY(ctx, hipMemcpy(out_microsteps, ctx->d_micro, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_resolver_iterations)
-        HIP_TRY(ctx, hipMemcpy(out_resolver_iterations, ctx->d_res, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_error_flags) HIP_TRY(ctx, hipMemcpy(out_error_flags, ctx->d_err, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, sg.download(rows, W, out_positions, out_collided, out_microsteps, out_resolver_iterations, out_error_flags));
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
     return FKS_OK;
 }
@@ -1957,19 +1817,10 @@ static fks_status simulate_batch_host(fks_context* ctx, const fks_batch::Inputs&
     const uint64_t N = b.total, R = b.rows;
     uint64_t NT = 0;
     for (uint64_t j = 0; j < b.num_jobs; ++j) NT += b.jobs()[j].n > 0 ? b.jobs()[j].num_targets * b.jobs()[j].num_legs : 0;
-    const uint64_t rows = std::max(N + NT, R);
-    if (rows > ctx->cap_particles) {
-        HIP_TRY(ctx, ensure(&ctx->d_starts, rows * W));
-        HIP_TRY(ctx, ensure(&ctx->d_out, rows * W));
-        HIP_TRY(ctx, ensure(&ctx->d_coll, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_micro, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_res, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_err, rows));
-        ctx->cap_particles = rows;
-    }
+    fks_buf::ParticleStaging& sg = ctx->stage;
+    HIP_TRY(ctx, sg.reserve_rows(std::max(N + NT, R), W)); /* starts also carries the waypoints */
     const size_t in_bytes = (N + NT) * W * sizeof(double);
-    const size_t q_bytes = R * W * sizeof(double), u_bytes = R * sizeof(uint32_t);
-    ctx->jobs_stage.resize(std::max(in_bytes, q_bytes + 3 * u_bytes + R));
+    ctx->jobs_stage.resize(std::max(in_bytes, fks_buf::HostRows::bytes(R, W)));
     double* h_in = reinterpret_cast<double*>(ctx->jobs_stage.data());
     fks_batch::Batch dev = b; /* the same jobs over the staging buffers */
     dev.converted.assign(b.jobs(), b.jobs() + b.num_jobs);
@@ -1979,25 +1830,17 @@ static fks_status simulate_batch_host(fks_context* ctx, const fks_batch::Inputs&
         const uint64_t nt = d.num_targets * d.num_legs;
         std::memcpy(h_in + at * W, d.starts, d.n * W * sizeof(double));
         std::memcpy(h_in + tat * W, d.waypoints, nt * W * sizeof(double));
-        d.starts = ctx->d_starts + at * W;
-        d.waypoints = ctx->d_starts + tat * W;
-        d.out_positions = ctx->d_out + oat * W;
-        d.out_collided = ctx->d_coll + oat;
-        d.out_microsteps = ctx->d_micro + oat;
-        d.out_resolver_iterations = ctx->d_res + oat;
-        d.out_error_flags = ctx->d_err + oat;
+        d.starts = sg.starts.get() + at * W;
+        d.waypoints = sg.starts.get() + tat * W;
+        sg.stage_outputs(&d, oat, W);
         at += d.n;
         tat += nt;
         oat += d.n * d.num_legs;
     }
-    HIP_TRY(ctx, hipMemcpy(ctx->d_starts, h_in, in_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(sg.starts.get(), h_in, in_bytes, hipMemcpyHostToDevice));
     st = run_batch(ctx, in, dev, nullptr, 1);
     if (st != FKS_OK) return st;
-    double* h_q = reinterpret_cast<double*>(ctx->jobs_stage.data());
-    uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + R * W);
-    uint32_t* h_res = h_micro + R;
-    uint32_t* h_err = h_res + R;
-    uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + R);
+    const fks_buf::HostRows h(ctx->jobs_stage.data(), R, W);
     bool want_coll = false, want_micro = false, want_res = false, want_err = false;
     for (uint64_t j = 0; j < b.num_jobs; ++j) {
         const fks_path_job& job = b.jobs()[j];
@@ -2007,21 +1850,18 @@ static fks_status simulate_batch_host(fks_context* ctx, const fks_batch::Inputs&
         want_res |= job.out_resolver_iterations != nullptr;
         want_err |= job.out_error_flags != nullptr;
     }
-    HIP_TRY(ctx, hipMemcpy(h_q, ctx->d_out, q_bytes, hipMemcpyDeviceToHost));
-    if (want_coll) HIP_TRY(ctx, hipMemcpy(h_coll, ctx->d_coll, R, hipMemcpyDeviceToHost));
-    if (want_micro) HIP_TRY(ctx, hipMemcpy(h_micro, ctx->d_micro, u_bytes, hipMemcpyDeviceToHost));
-    if (want_res) HIP_TRY(ctx, hipMemcpy(h_res, ctx->d_res, u_bytes, hipMemcpyDeviceToHost));
-    if (want_err) HIP_TRY(ctx, hipMemcpy(h_err, ctx->d_err, u_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, sg.download(R, W, h.q, want_coll ? h.coll : nullptr, want_micro ? h.micro : nullptr, want_res ? h.res : nullptr,
+                             want_err ? h.err : nullptr));
     oat = 0;
     for (uint64_t j = 0; j < b.num_jobs; ++j) {
         const fks_path_job& job = b.jobs()[j];
         if (job.n == 0) continue;
         const uint64_t r = job.n * job.num_legs;
-        std::memcpy(job.out_positions, h_q + oat * W, r * W * sizeof(double));
-        if (job.out_collided) std::memcpy(job.out_collided, h_coll + oat, r);
-        if (job.out_microsteps) std::memcpy(job.out_microsteps, h_micro + oat, r * sizeof(uint32_t));
-        if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations, h_res + oat, r * sizeof(uint32_t));
-        if (job.out_error_flags) std::memcpy(job.out_error_flags, h_err + oat, r * sizeof(uint32_t));
+        std::memcpy(job.out_positions, h.q + oat * W, r * W * sizeof(double));
+        if (job.out_collided) std::memcpy(job.out_collided, h.coll + oat, r);
+        if (job.out_microsteps) std::memcpy(job.out_microsteps, h.micro + oat, r * sizeof(uint32_t));
+        if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations, h.res + oat, r * sizeof(uint32_t));
+        if (job.out_error_flags) std::memcpy(job.out_error_flags, h.err + oat, r * sizeof(uint32_t));
         oat += r;
     }
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
@@ -2067,25 +1907,12 @@ fks_status fks_forward_simulate_policy(fks_context* ctx, const double* starts, u
     const uint64_t M = table->num_entries, rows = n * max_legs, sel = n * (max_legs + 1);
     /* in doubles: starts, keys, targets, flags (two to a double) */
     const uint64_t in_words = (n + 2 * M) * W + (table->flags ? (M + 1) / 2 : 0);
-    if (rows > ctx->cap_particles) {
-        HIP_TRY(ctx, ensure(&ctx->d_starts, rows * W));
-        HIP_TRY(ctx, ensure(&ctx->d_out, rows * W));
-        HIP_TRY(ctx, ensure(&ctx->d_coll, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_micro, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_res, rows));
-        HIP_TRY(ctx, ensure(&ctx->d_err, rows));
-        ctx->cap_particles = rows;
-    }
-    if (in_words > ctx->cap_policy_in) { /* a large table grows this buffer alone */
-        HIP_TRY(ctx, ensure(&ctx->d_policy_in, in_words));
-        ctx->cap_policy_in = in_words;
-    }
-    if (sel > ctx->cap_policy_sel) {
-        HIP_TRY(ctx, ensure(&ctx->d_policy_choice, sel));
-        HIP_TRY(ctx, ensure(&ctx->d_policy_distance, sel));
-        HIP_TRY(ctx, ensure(&ctx->d_policy_legs, sel)); /* >= n, whatever the next call's legs */
-        ctx->cap_policy_sel = sel;
-    }
+    fks_buf::ParticleStaging& sg = ctx->stage;
+    HIP_TRY(ctx, sg.reserve_rows(rows, W));
+    HIP_TRY(ctx, ctx->d_policy_in.reserve(in_words)); /* a large table grows this buffer alone */
+    HIP_TRY(ctx, ctx->d_policy_choice.reserve(sel));
+    HIP_TRY(ctx, ctx->d_policy_distance.reserve(sel));
+    HIP_TRY(ctx, ctx->d_policy_legs.reserve(sel)); /* >= n, whatever the next call's legs */
     ctx->jobs_stage.resize(in_words * sizeof(double));
     double* h_in = reinterpret_cast<double*>(ctx->jobs_stage.data());
     std::memcpy(h_in, starts, n * W * sizeof(double));
@@ -2095,31 +1922,23 @@ fks_status fks_forward_simulate_policy(fks_context* ctx, const double* starts, u
         h_in[in_words - 1] = 0.0; /* the odd entry's other half */
         std::memcpy(h_in + (n + 2 * M) * W, table->flags, M * sizeof(uint32_t));
     }
-    HIP_TRY(ctx, hipMemcpy(ctx->d_policy_in, h_in, in_words * sizeof(double), hipMemcpyHostToDevice));
+    double* d_in = ctx->d_policy_in.get();
+    HIP_TRY(ctx, hipMemcpy(d_in, h_in, in_words * sizeof(double), hipMemcpyHostToDevice));
     fks_path_job& dev = b.converted[0]; /* the same roll-out over the staging buffers */
-    dev.starts = ctx->d_policy_in;
-    dev.out_positions = ctx->d_out;
-    dev.out_collided = ctx->d_coll;
-    dev.out_microsteps = ctx->d_micro;
-    dev.out_resolver_iterations = ctx->d_res;
-    dev.out_error_flags = ctx->d_err;
-    b.table.keys = ctx->d_policy_in + n * W;
-    b.table.targets = ctx->d_policy_in + (n + M) * W;
-    b.table.flags = table->flags ? reinterpret_cast<const uint32_t*>(ctx->d_policy_in + (n + 2 * M) * W) : nullptr;
-    b.out_choice = ctx->d_policy_choice;
-    b.out_distance = ctx->d_policy_distance;
-    b.out_legs_run = ctx->d_policy_legs;
+    dev.starts = d_in;
+    sg.stage_outputs(&dev, 0, W);
+    b.table.keys = d_in + n * W;
+    b.table.targets = d_in + (n + M) * W;
+    b.table.flags = table->flags ? reinterpret_cast<const uint32_t*>(d_in + (n + 2 * M) * W) : nullptr;
+    b.out_choice = ctx->d_policy_choice.get();
+    b.out_distance = ctx->d_policy_distance.get();
+    b.out_legs_run = ctx->d_policy_legs.get();
     st = run_batch(ctx, in, b, nullptr, 1);
     if (st != FKS_OK) return st;
-    HIP_TRY(ctx, hipMemcpy(out_positions, ctx->d_out, rows * W * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_collided) HIP_TRY(ctx, hipMemcpy(out_collided, ctx->d_coll, rows, hipMemcpyDeviceToHost));
-    if (out_microsteps) HIP_TRY(ctx, hipMemcpy(out_microsteps, ctx->d_micro, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_resolver_iterations)
-        HIP_TRY(ctx, hipMemcpy(out_resolver_iterations, ctx->d_res, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_error_flags) HIP_TRY(ctx, hipMemcpy(out_error_flags, ctx->d_err, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out_choice, ctx->d_policy_choice, sel * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_distance) HIP_TRY(ctx, hipMemcpy(out_distance, ctx->d_policy_distance, sel * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_legs_run) HIP_TRY(ctx, hipMemcpy(out_legs_run, ctx->d_policy_legs, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, sg.download(rows, W, out_positions, out_collided, out_microsteps, out_resolver_iterations, out_error_flags));
+    HIP_TRY(ctx, hipMemcpy(out_choice, b.out_choice, sel * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_distance) HIP_TRY(ctx, hipMemcpy(out_distance, b.out_distance, sel * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_legs_run) HIP_TRY(ctx, hipMemcpy(out_legs_run, b.out_legs_run, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     ctx->last.call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->call_start).count();
     return FKS_OK;
 }
@@ -2131,33 +1950,23 @@ static fks_status cluster_device(fks_context* ctx, const fks_batch::ClusterPlan&
                                  uint32_t* d_out_num_clusters, hipStream_t s, int32_t synchronize) {
     if (!plan.launch) return FKS_OK;
     const size_t G = (size_t)plan.num_groups, words = 2 * (G + 1);
-    if (words > ctx->cap_cluster_off) {
-        if (ctx->h_cluster_off) (void)hipHostFree(ctx->h_cluster_off);
-        ctx->h_cluster_off = nullptr;
-        ctx->cap_cluster_off = 0;
-        HIP_TRY(ctx, ensure(&ctx->d_cluster_off, words));
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_cluster_off, words * sizeof(uint64_t), 0));
-        ctx->cap_cluster_off = words;
-    }
-    if (plan.work_words > ctx->cap_cluster_work) {
-        HIP_TRY(ctx, ensure(&ctx->d_cluster_work, (size_t)plan.work_words));
-        ctx->cap_cluster_work = (size_t)plan.work_words;
-    }
+    HIP_TRY(ctx, ctx->cluster_off.reserve(words));
+    if (plan.work_words) HIP_TRY(ctx, ctx->d_cluster_work.reserve((size_t)plan.work_words));
     /* the previous call has settled, so the pinned copy is free */
-    std::memcpy(ctx->h_cluster_off, group_begin, (G + 1) * sizeof(uint64_t));
-    std::memcpy(ctx->h_cluster_off + (G + 1), plan.mat_begin.data(), (G + 1) * sizeof(uint64_t));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cluster_off, ctx->h_cluster_off, words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    std::memcpy(ctx->cluster_off.host(), group_begin, (G + 1) * sizeof(uint64_t));
+    std::memcpy(ctx->cluster_off.host() + (G + 1), plan.mat_begin.data(), (G + 1) * sizeof(uint64_t));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->cluster_off.dev(), ctx->cluster_off.host(), words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     fksd::ClusterArgs a;
     std::memset(&a, 0, sizeof(a));
     a.R = ctx->R;
     a.configs = d_configs;
-    a.offsets = ctx->d_cluster_off;
+    a.offsets = ctx->cluster_off.dev();
     a.num_groups = plan.num_groups;
     a.threshold = threshold;
     a.out_distances = d_out_distances;
     a.out_labels = d_out_labels;
     a.out_num_clusters = d_out_num_clusters;
-    a.work = plan.work_words ? ctx->d_cluster_work : nullptr;
+    a.work = plan.work_words ? ctx->d_cluster_work.get() : nullptr;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(plan.num_groups, 1u << 16);
     void (*kernel)(const fksd::ClusterArgs) =
         ctx->R.type == FKS_ROBOT_LINKED ? fks_cluster_linked : (ctx->R.type == FKS_ROBOT_SE2 ? fks_cluster_se2 : fks_cluster_se3);
@@ -2203,35 +2012,23 @@ fks_status fks_cluster_configs_ctx(fks_context* ctx, const double* configs, cons
     if (!plan.launch) return FKS_OK;
     const size_t W = (size_t)ctx->R.W, N = (size_t)plan.total, G = (size_t)plan.num_groups;
     const size_t in_words = N * W, mat_words = (size_t)plan.mat_begin[G];
-    if (in_words > ctx->cap_cluster_in) {
-        HIP_TRY(ctx, ensure(&ctx->d_cluster_in, in_words));
-        ctx->cap_cluster_in = in_words;
-    }
-    if (out_distances && mat_words > ctx->cap_cluster_mat) {
-        HIP_TRY(ctx, ensure(&ctx->d_cluster_mat, mat_words));
-        ctx->cap_cluster_mat = mat_words;
-    }
-    if (out_labels && N > ctx->cap_cluster_labels) {
-        HIP_TRY(ctx, ensure(&ctx->d_cluster_labels, N));
-        ctx->cap_cluster_labels = N;
-    }
-    if (out_num_clusters && G > ctx->cap_cluster_counts) {
-        HIP_TRY(ctx, ensure(&ctx->d_cluster_counts, G));
-        ctx->cap_cluster_counts = G;
-    }
+    HIP_TRY(ctx, ctx->d_cluster_in.reserve(in_words));
+    if (out_distances) HIP_TRY(ctx, ctx->d_cluster_mat.reserve(mat_words));
+    if (out_labels) HIP_TRY(ctx, ctx->d_cluster_labels.reserve(N));
+    if (out_num_clusters) HIP_TRY(ctx, ctx->d_cluster_counts.reserve(G));
+    double* d_mat = out_distances ? ctx->d_cluster_mat.get() : nullptr;
+    uint32_t* d_labels = out_labels ? ctx->d_cluster_labels.get() : nullptr;
+    uint32_t* d_counts = out_num_clusters ? ctx->d_cluster_counts.get() : nullptr;
     /* configs [N][W] goes up in one copy */
-    if (in_words && configs) HIP_TRY(ctx, hipMemcpy(ctx->d_cluster_in, configs, in_words * sizeof(double), hipMemcpyHostToDevice));
-    const fks_status run = cluster_device(ctx, plan, ctx->d_cluster_in, group_begin, threshold,
-                                          out_distances ? ctx->d_cluster_mat : nullptr, out_labels ? ctx->d_cluster_labels : nullptr,
-                                          out_num_clusters ? ctx->d_cluster_counts : nullptr, nullptr, 1);
+    if (in_words && configs) HIP_TRY(ctx, hipMemcpy(ctx->d_cluster_in.get(), configs, in_words * sizeof(double), hipMemcpyHostToDevice));
+    const fks_status run = cluster_device(ctx, plan, ctx->d_cluster_in.get(), group_begin, threshold, d_mat, d_labels, d_counts, nullptr, 1);
     if (run != FKS_OK) return run;
-    if (out_distances && mat_words)
-        HIP_TRY(ctx, hipMemcpy(out_distances, ctx->d_cluster_mat, mat_words * sizeof(double), hipMemcpyDeviceToHost));
+    if (d_mat && mat_words) HIP_TRY(ctx, hipMemcpy(out_distances, d_mat, mat_words * sizeof(double), hipMemcpyDeviceToHost));
     /* labels before group_begin[0] belong to no group: the caller's stay as they are */
     const size_t first = (size_t)group_begin[0];
-    if (out_labels && N > first)
-        HIP_TRY(ctx, hipMemcpy(out_labels + first, ctx->d_cluster_labels + first, (N - first) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_num_clusters) HIP_TRY(ctx, hipMemcpy(out_num_clusters, ctx->d_cluster_counts, G * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (d_labels && N > first)
+        HIP_TRY(ctx, hipMemcpy(out_labels + first, d_labels + first, (N - first) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (d_counts) HIP_TRY(ctx, hipMemcpy(out_num_clusters, d_counts, G * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return FKS_OK;
 }
 
@@ -2275,6 +2072,14 @@ fks_status fks_forward_simulate_path_jobs(fks_context* ctx, const fks_path_job* 
 
 }  // extern "C"
 
+/* a block of `count` elements, all zero (a trace's records past a particle's count stay zero, as
+ * in the caller's view) */
+template <typename T>
+static hipError_t zeroed(DeviceBuffer<T>& b, size_t count) {
+    const hipError_t e = b.reserve(count);
+    return e != hipSuccess ? e : hipMemset(b.get(), 0, b.capacity() * sizeof(T));
+}
+
 /* the traced calls: device trace buffers around simulate_host, copied to the caller's */
 static fks_status simulate_traced(fks_context* ctx, const double* starts, uint64_t n, const double* targets, uint64_t num_targets,
                                   int32_t allow_contacts, double* controller_state, double* out_positions, uint8_t* out_collided,
@@ -2289,31 +2094,18 @@ static fks_status simulate_traced(fks_context* ctx, const double* starts, uint64
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t D = (size_t)ctx->R.D, W = (size_t)ctx->R.W;
     const size_t ns = (size_t)n * trace->step_capacity, nc = (size_t)n * trace->config_capacity;
-    TraceDev tr{};
-    tr.step_cap = trace->step_capacity;
-    tr.cfg_cap = trace->config_capacity;
-    std::vector<void*> allocs;
-    auto alloc = [&](void** p, size_t bytes) {
-        hipError_t e = hipMalloc(p, bytes > 0 ? bytes : 8);
-        if (e == hipSuccess) allocs.push_back(*p);
-        /* records past a particle's count stay zero, as in the caller's view */
-        if (e == hipSuccess) e = hipMemset(*p, 0, bytes > 0 ? bytes : 8);
-        return e;
-    };
-    auto release = [&]() {
-        for (void* p : allocs) (void)hipFree(p);
-    };
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = alloc((void**)&tr.inputs, ns * 2 * D * sizeof(double));
-    if (e == hipSuccess) e = alloc((void**)&tr.micro, ns * sizeof(uint32_t));
-    if (e == hipSuccess) e = alloc((void**)&tr.cfg, nc * W * sizeof(double));
-    if (e == hipSuccess) e = alloc((void**)&tr.tags, nc * 3 * sizeof(uint32_t));
-    if (e == hipSuccess) e = alloc((void**)&tr.nsteps, (size_t)n * sizeof(uint32_t));
-    if (e == hipSuccess) e = alloc((void**)&tr.ncfg, (size_t)n * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        release();
-        return hip_fail(ctx, e, "trace buffers");
-    }
+    /* the call's own buffers, given back when it returns */
+    DeviceBuffer<double> d_inputs, d_cfg;
+    DeviceBuffer<uint32_t> d_micro, d_tags, d_nsteps, d_ncfg;
+    hipError_t e = zeroed(d_inputs, ns * 2 * D);
+    if (e == hipSuccess) e = zeroed(d_micro, ns);
+    if (e == hipSuccess) e = zeroed(d_cfg, nc * W);
+    if (e == hipSuccess) e = zeroed(d_tags, nc * 3);
+    if (e == hipSuccess) e = zeroed(d_nsteps, (size_t)n);
+    if (e == hipSuccess) e = zeroed(d_ncfg, (size_t)n);
+    if (e != hipSuccess) return hip_fail(ctx, e, "trace buffers");
+    const TraceDev tr = {d_inputs.get(), d_micro.get(), d_cfg.get(),          d_tags.get(),
+                         d_nsteps.get(), d_ncfg.get(),  trace->step_capacity, trace->config_capacity};
     fks_status st = simulate_host(ctx, starts, n, targets, num_targets, allow_contacts, out_positions, out_collided,
                                   out_microsteps, out_resolver_iterations, out_error_flags, &tr, controller_state);
     if (st == FKS_OK && n > 0) {
@@ -2336,7 +2128,6 @@ static fks_status simulate_traced(fks_context* ctx, const double* starts, uint64
             }
         }
     }
-    release();
     return st;
 }
 
@@ -2389,19 +2180,11 @@ fks_status fks_kinematics(fks_context* ctx, int32_t mode, const double* configs,
     const size_t W = (size_t)ctx->R.W, D = (size_t)ctx->R.D;
     const size_t per_out = (mode == FKS_KIN_LINK_TRANSFORMS) ? 12 * (size_t)ctx->R.L
                                                              : (mode == FKS_KIN_POINTS ? 3 * (size_t)ctx->R.P : W);
-    double *d_cfg = nullptr, *d_in = nullptr, *d_out = nullptr;
-    auto release = [&]() {
-        if (d_cfg) (void)hipFree(d_cfg);
-        if (d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-    };
-    hipError_t e = dev_upload(&d_cfg, configs, (size_t)n * W);
-    if (e == hipSuccess && mode == FKS_KIN_APPLY_CONTROL_INPUT) e = dev_upload(&d_in, inputs, (size_t)n * D);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, (size_t)n * per_out * sizeof(double));
-    if (e != hipSuccess) {
-        release();
-        return hip_fail(ctx, e, "kinematics buffers");
-    }
+    DeviceBuffer<double> d_cfg, d_in, d_out; /* the call's own, given back when it returns */
+    hipError_t e = upload(d_cfg, configs, (size_t)n * W);
+    if (e == hipSuccess && mode == FKS_KIN_APPLY_CONTROL_INPUT) e = upload(d_in, inputs, (size_t)n * D);
+    if (e == hipSuccess) e = d_out.reserve((size_t)n * per_out);
+    if (e != hipSuccess) return hip_fail(ctx, e, "kinematics buffers");
     fksd::SimArgs a;
     std::memset(&a, 0, sizeof(a));
     a.sdf_g = ctx->sdf_g;
@@ -2409,29 +2192,28 @@ fks_status fks_kinematics(fks_context* ctx, int32_t mode, const double* configs,
     a.env_g = ctx->env_g;
     a.R = ctx->R;
     a.S = ctx->params;
-    a.starts = d_cfg;
-    a.targets = d_in;
+    a.starts = d_cfg.get();
+    a.targets = d_in.get();
     a.n = n;
-    a.scratch = ctx->d_scratch;
+    a.scratch = ctx->d_scratch.get();
     a.scratch_per_wave = ctx->scratch_per_wave;
     a.row_cap = 3u * (uint32_t)ctx->R.P;
     a.L = fksd::make_lds_layout(ctx->R.L, ctx->R.J, ctx->R.D, ctx->R.W, ctx->R.G, ctx->R.nrounds, ctx->fk_pair, ctx->lean);
     a.SL = fksd::make_scratch_layout(a.row_cap, ctx->R.D, ctx->R.P, ctx->R.G);
     a.kin_mode = mode;
-    a.kin_out = d_out;
-    *ctx->h_args = a;
-    e = hipMemcpy(ctx->d_args, ctx->h_args, sizeof(a), hipMemcpyHostToDevice);
+    a.kin_out = d_out.get();
+    *ctx->args.host() = a;
+    e = hipMemcpy(ctx->args.dev(), ctx->args.host(), sizeof(a), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const uint64_t groups_needed = (n + ctx->waves_per_group - 1) / ctx->waves_per_group;
         const uint32_t grid = (uint32_t)((groups_needed < (uint64_t)ctx->grid_groups) ? groups_needed : ctx->grid_groups);
         sim_kernel_t k = (ctx->R.type == FKS_ROBOT_SE2) ? fks_kinematics_se2
                                                         : (ctx->R.type == FKS_ROBOT_SE3 ? fks_kinematics_se3 : fks_kinematics_linked);
         hipLaunchKernelGGL(k, dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, nullptr,
-                           static_cast<const fksd::SimArgs*>(ctx->d_args));
+                           static_cast<const fksd::SimArgs*>(ctx->args.dev()));
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * per_out * sizeof(double), hipMemcpyDeviceToHost);
-    release();
+    if (e == hipSuccess) e = hipMemcpy(out, d_out.get(), (size_t)n * per_out * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(ctx, e, "fks_kinematics");
     return FKS_OK;
 }
@@ -2664,16 +2446,12 @@ fks_status fks_selftest_math(int32_t device, uint64_t n, uint64_t* out_mismatche
         host[8 * i + 6] = fks_math::enforce_continuous_revolute_bounds(x / y); /* glibc fmod vs the kernel's wrap */
         host[8 * i + 7] = (x * y + x) * y - x * x;
     }
-    double *da = nullptr, *db = nullptr, *dout = nullptr;
-    if (dev_upload(&da, a.data(), n) != hipSuccess || dev_upload(&db, b.data(), n) != hipSuccess ||
-        hipMalloc((void**)&dout, 8 * n * sizeof(double)) != hipSuccess)
+    DeviceBuffer<double> da, db, dout;
+    if (upload(da, a.data(), n) != hipSuccess || upload(db, b.data(), n) != hipSuccess || dout.reserve(8 * n) != hipSuccess)
         return FKS_ERR_HIP;
-    hipLaunchKernelGGL(fks_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, da, db, dout, n);
-    hipError_t e = hipMemcpy(dev.data(), dout, 8 * n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(da);
-    (void)hipFree(db);
-    (void)hipFree(dout);
-    if (e != hipSuccess) return FKS_ERR_HIP;
+    hipLaunchKernelGGL(fks_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr,
+                       static_cast<const double*>(da.get()), static_cast<const double*>(db.get()), dout.get(), n);
+    if (hipMemcpy(dev.data(), dout.get(), 8 * n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return FKS_ERR_HIP;
     uint64_t mism = 0;
     for (uint64_t i = 0; i < 8 * n; ++i)
         if (std::memcmp(&host[i], &dev[i], sizeof(double)) != 0) mism++;

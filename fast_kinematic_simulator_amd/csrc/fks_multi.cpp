@@ -34,29 +34,20 @@
 
 #include "fks_capi.h"
 #include "fks_batch.h"
+#include "fks_buffers.h"
 
 struct fks_multi_context {
     struct Device {
         int32_t device = 0;
         fks_context* ctx = nullptr;
         hipStream_t stream = nullptr;
-        double* d_starts = nullptr;
-        double* d_targets = nullptr;
-        double* d_out = nullptr;
-        uint8_t* d_coll = nullptr;
-        uint32_t* d_micro = nullptr;
-        uint32_t* d_res = nullptr;
-        uint32_t* d_err = nullptr;
-        size_t cap = 0, cap_targets = 0;
-        /* pinned host staging of the shard: inputs (starts, targets), outputs (positions,
-         * then collided bytes, microsteps, resolver iterations, error bits) */
-        unsigned char* h_in = nullptr;
-        unsigned char* h_out = nullptr;
-        size_t cap_h_in = 0, cap_h_out = 0;
+        fks_buf::ParticleStaging stage; /* the shard in HBM */
+        /* pinned host staging of the shard: inputs (starts, targets), outputs (fks_buf::HostRows) */
+        fks_buf::PinnedBuffer<unsigned char> h_in, h_out;
         fks_status status = FKS_OK; /* the device thread's outcome */
         std::string error;
         fks_call_counters counters{};
-    };
+    }; /* move-only, as the buffers it owns */
     std::vector<Device> devices;
     std::string last_error;
     uint64_t call_index = 0;
@@ -75,32 +66,11 @@ fks_status mctx(fks_multi_context* m, fks_status st, const fks_context* ctx, con
     return mfail(m, st, std::string(where) + ": " + fks_status_string(st) + " (" + fks_get_last_error(ctx) + ")");
 }
 
-template <typename T>
-hipError_t grow(T** p, size_t count) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    return hipMalloc((void**)p, (count > 0 ? count : 1) * sizeof(T));
-}
-hipError_t grow_pinned(unsigned char** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap && *p) return hipSuccess;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const hipError_t e = hipHostMalloc((void**)p, bytes > 0 ? bytes : 1, hipHostMallocDefault);
-    if (e == hipSuccess) *cap = bytes;
-    return e;
-}
-
 void free_device(fks_multi_context::Device& d) {
-    (void)hipSetDevice(d.device);
-    void* ptrs[] = {d.d_starts, d.d_targets, d.d_out, d.d_coll, d.d_micro, d.d_res, d.d_err};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (d.h_in) (void)hipHostFree(d.h_in);
-    if (d.h_out) (void)hipHostFree(d.h_out);
+    (void)hipSetDevice(d.device); /* before anything is freed */
     if (d.stream) (void)hipStreamDestroy(d.stream);
-    if (d.ctx) fks_destroy(d.ctx);
-    d = fks_multi_context::Device();
+    if (d.ctx) fks_destroy(d.ctx); /* selects the same device */
+    d = fks_multi_context::Device(); /* the buffers go with their owners */
 }
 
 int32_t active_count(const fks_multi_context* m) {
@@ -177,7 +147,7 @@ fks_status fks_create_multi(const fks_environment* env, const fks_solver_params*
         fks_status st = fks_create(env, params, simulation_controller_frequency, prng_seed, debug_level, d.device, &d.ctx);
         if (st == FKS_OK && hipSetDevice(d.device) != hipSuccess) st = FKS_ERR_HIP;
         if (st == FKS_OK && hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking) != hipSuccess) st = FKS_ERR_HIP;
-        m->devices.push_back(d);
+        m->devices.push_back(std::move(d));
         if (st != FKS_OK) {
             fks_destroy_multi(m);
             return st;
@@ -242,63 +212,43 @@ static fks_status multi_simulate(fks_multi_context* m, const double* starts, uin
         DCTX(d, fks_set_call_index(d.ctx, call), "fks_set_call_index");
         DHIP(d, hipSetDevice(d.device));
         const uint64_t rows = k * K; /* the shard's output rows: a path's are leg-major [K][k] */
-        if (rows > d.cap) {
-            DHIP(d, grow(&d.d_starts, rows * W));
-            DHIP(d, grow(&d.d_out, rows * W));
-            DHIP(d, grow(&d.d_coll, rows));
-            DHIP(d, grow(&d.d_micro, rows));
-            DHIP(d, grow(&d.d_res, rows));
-            DHIP(d, grow(&d.d_err, rows));
-            d.cap = rows;
-        }
+        fks_buf::ParticleStaging& sg = d.stage;
+        DHIP(d, sg.reserve_rows(rows, W));
         const uint64_t nt = (num_targets == n) ? k : 1; /* per leg */
-        if (nt * K > d.cap_targets) {
-            DHIP(d, grow(&d.d_targets, nt * K * W));
-            d.cap_targets = nt * K;
-        }
+        DHIP(d, sg.reserve_targets(nt * K, W));
         if (k == 0) {
             DCTX(d, fks_get_last_call_counters(d.ctx, &d.counters), "fks_get_last_call_counters"); /* settles */
             std::memset(&d.counters, 0, sizeof(d.counters));
             return;
         }
-        const size_t in_bytes = (k + nt * K) * W * sizeof(double);
-        const size_t out_bytes = rows * W * sizeof(double) + rows * (1 + 3 * sizeof(uint32_t));
-        DHIP(d, grow_pinned(&d.h_in, &d.cap_h_in, in_bytes));
-        DHIP(d, grow_pinned(&d.h_out, &d.cap_h_out, out_bytes));
-        double* h_starts = reinterpret_cast<double*>(d.h_in);
+        DHIP(d, d.h_in.reserve((k + nt * K) * W * sizeof(double)));
+        DHIP(d, d.h_out.reserve(fks_buf::HostRows::bytes(rows, W)));
+        double* h_starts = reinterpret_cast<double*>(d.h_in.get());
         double* h_targets = h_starts + k * W;
         std::memcpy(h_starts, starts + lo * W, k * W * sizeof(double));
         for (uint64_t leg = 0; leg < K; ++leg) /* the shard's rows of every leg's targets */
             std::memcpy(h_targets + leg * nt * W, targets + (leg * num_targets + (num_targets == n ? lo : 0)) * W,
                         nt * W * sizeof(double));
-        DHIP(d, hipMemcpyAsync(d.d_starts, h_starts, k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
-        DHIP(d, hipMemcpyAsync(d.d_targets, h_targets, nt * K * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
+        DHIP(d, hipMemcpyAsync(sg.starts.get(), h_starts, k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
+        DHIP(d, hipMemcpyAsync(sg.targets.get(), h_targets, nt * K * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
         if (path)
-            DCTX(d, fks_forward_simulate_path_device(d.ctx, d.d_starts, k, d.d_targets, legs, nt, lo, allow_contacts, d.d_out, d.d_coll,
-                                                     d.d_micro, d.d_res, d.d_err, d.stream, 0),
+            DCTX(d, fks_forward_simulate_path_device(d.ctx, sg.starts.get(), k, sg.targets.get(), legs, nt, lo, allow_contacts,
+                                                     sg.out.get(), sg.coll.get(), sg.micro.get(), sg.res.get(), sg.err.get(), d.stream, 0),
                  "fks_forward_simulate_path_device");
         else
-            DCTX(d, fks_forward_simulate_device(d.ctx, d.d_starts, k, d.d_targets, nt, lo, allow_contacts, d.d_out, d.d_coll, d.d_micro,
-                                                d.d_res, d.d_err, d.stream, 0),
+            DCTX(d, fks_forward_simulate_device(d.ctx, sg.starts.get(), k, sg.targets.get(), nt, lo, allow_contacts, sg.out.get(),
+                                                sg.coll.get(), sg.micro.get(), sg.res.get(), sg.err.get(), d.stream, 0),
                  "fks_forward_simulate_device");
-        double* h_q = reinterpret_cast<double*>(d.h_out);
-        uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + rows * W);
-        uint32_t* h_res = h_micro + rows;
-        uint32_t* h_err = h_res + rows;
-        uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + rows);
-        DHIP(d, hipMemcpyAsync(h_q, d.d_out, rows * W * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_micro, d.d_micro, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_res, d.d_res, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_err, d.d_err, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_coll, d.d_coll, rows, hipMemcpyDeviceToHost, d.stream));
+        const fks_buf::HostRows h(d.h_out.get(), rows, W);
+        DHIP(d, sg.download_async(rows, W, h, d.stream));
         DHIP(d, hipStreamSynchronize(d.stream));
         for (uint64_t leg = 0; leg < K; ++leg) {
             const uint64_t src = leg * k, dst = leg * n + lo;
-            std::memcpy(out_positions + dst * W, h_q + src * W, k * W * sizeof(double));
-            if (out_collided) std::memcpy(out_collided + dst, h_coll + src, k);
-            if (out_microsteps) std::memcpy(out_microsteps + dst, h_micro + src, k * sizeof(uint32_t));
-            if (out_resolver_iterations) std::memcpy(out_resolver_iterations + dst, h_res + src, k * sizeof(uint32_t));
-            if (out_error_flags) std::memcpy(out_error_flags + dst, h_err + src, k * sizeof(uint32_t));
+            std::memcpy(out_positions + dst * W, h.q + src * W, k * W * sizeof(double));
+            if (out_collided) std::memcpy(out_collided + dst, h.coll + src, k);
+            if (out_microsteps) std::memcpy(out_microsteps + dst, h.micro + src, k * sizeof(uint32_t));
+            if (out_resolver_iterations) std::memcpy(out_resolver_iterations + dst, h.res + src, k * sizeof(uint32_t));
+            if (out_error_flags) std::memcpy(out_error_flags + dst, h.err + src, k * sizeof(uint32_t));
         }
         DCTX(d, fks_get_last_call_counters(d.ctx, &d.counters), "fks_get_last_call_counters"); /* settles the launch */
     });
@@ -394,24 +344,12 @@ static fks_status multi_batch(fks_multi_context* m, fks_batch::Batch& b) {
         }
         DCTX(d, fks_set_call_index(d.ctx, call), "fks_set_call_index");
         DHIP(d, hipSetDevice(d.device));
-        if (rows > d.cap) {
-            DHIP(d, grow(&d.d_starts, rows * W));
-            DHIP(d, grow(&d.d_out, rows * W));
-            DHIP(d, grow(&d.d_coll, rows));
-            DHIP(d, grow(&d.d_micro, rows));
-            DHIP(d, grow(&d.d_res, rows));
-            DHIP(d, grow(&d.d_err, rows));
-            d.cap = rows;
-        }
-        if (nt > d.cap_targets) {
-            DHIP(d, grow(&d.d_targets, nt * W));
-            d.cap_targets = nt;
-        }
-        const size_t in_bytes = (k + nt) * W * sizeof(double);
-        const size_t out_bytes = rows * W * sizeof(double) + rows * (1 + 3 * sizeof(uint32_t));
-        DHIP(d, grow_pinned(&d.h_in, &d.cap_h_in, in_bytes));
-        DHIP(d, grow_pinned(&d.h_out, &d.cap_h_out, out_bytes));
-        double* h_starts = reinterpret_cast<double*>(d.h_in);
+        fks_buf::ParticleStaging& sg = d.stage;
+        DHIP(d, sg.reserve_rows(rows, W));
+        DHIP(d, sg.reserve_targets(nt, W));
+        DHIP(d, d.h_in.reserve((k + nt) * W * sizeof(double)));
+        DHIP(d, d.h_out.reserve(fks_buf::HostRows::bytes(rows, W)));
+        double* h_starts = reinterpret_cast<double*>(d.h_in.get());
         double* h_targets = h_starts + k * W;
         uint64_t at = 0, tat = 0, oat = 0;
         for (uint64_t j = 0; j < num_jobs; ++j) {
@@ -423,20 +361,16 @@ static fks_status multi_batch(fks_multi_context* m, fks_batch::Batch& b) {
             for (uint64_t leg = 0; leg < s.num_legs; ++leg) /* the sub-range's rows of every leg's waypoints */
                 std::memcpy(h_targets + (tat + leg * s.num_targets) * W, job.waypoints + (leg * job.num_targets + from) * W,
                             s.num_targets * W * sizeof(double));
-            s.starts = d.d_starts + at * W;
-            s.waypoints = d.d_targets + tat * W;
-            s.out_positions = d.d_out + oat * W;
-            s.out_collided = d.d_coll + oat;
-            s.out_microsteps = d.d_micro + oat;
-            s.out_resolver_iterations = d.d_res + oat;
-            s.out_error_flags = d.d_err + oat;
+            s.starts = sg.starts.get() + at * W;
+            s.waypoints = sg.targets.get() + tat * W;
+            sg.stage_outputs(&s, oat, W);
             at += s.n;
             tat += s.num_targets * s.num_legs;
             oat += s.n * s.num_legs;
         }
         if (k > 0) {
-            DHIP(d, hipMemcpyAsync(d.d_starts, h_starts, k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
-            DHIP(d, hipMemcpyAsync(d.d_targets, h_targets, nt * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
+            DHIP(d, hipMemcpyAsync(sg.starts.get(), h_starts, k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
+            DHIP(d, hipMemcpyAsync(sg.targets.get(), h_targets, nt * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
         }
         if (b.form == fks_batch::JOBS) {
             std::vector<fks_job> as_jobs((size_t)num_jobs);
@@ -451,16 +385,8 @@ static fks_status multi_batch(fks_multi_context* m, fks_batch::Batch& b) {
             std::memset(&d.counters, 0, sizeof(d.counters));
             return;
         }
-        double* h_q = reinterpret_cast<double*>(d.h_out);
-        uint32_t* h_micro = reinterpret_cast<uint32_t*>(h_q + rows * W);
-        uint32_t* h_res = h_micro + rows;
-        uint32_t* h_err = h_res + rows;
-        uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + rows);
-        DHIP(d, hipMemcpyAsync(h_q, d.d_out, rows * W * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_micro, d.d_micro, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_res, d.d_res, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_err, d.d_err, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_coll, d.d_coll, rows, hipMemcpyDeviceToHost, d.stream));
+        const fks_buf::HostRows h(d.h_out.get(), rows, W);
+        DHIP(d, sg.download_async(rows, W, h, d.stream));
         DHIP(d, hipStreamSynchronize(d.stream));
         oat = 0;
         for (uint64_t j = 0; j < num_jobs; ++j) {
@@ -469,11 +395,11 @@ static fks_status multi_batch(fks_multi_context* m, fks_batch::Batch& b) {
             if (s.n == 0) continue;
             for (uint64_t leg = 0; leg < s.num_legs; ++leg) {
                 const uint64_t src = oat + leg * s.n, dst = leg * job.n + row0[j];
-                std::memcpy(job.out_positions + dst * W, h_q + src * W, s.n * W * sizeof(double));
-                if (job.out_collided) std::memcpy(job.out_collided + dst, h_coll + src, s.n);
-                if (job.out_microsteps) std::memcpy(job.out_microsteps + dst, h_micro + src, s.n * sizeof(uint32_t));
-                if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations + dst, h_res + src, s.n * sizeof(uint32_t));
-                if (job.out_error_flags) std::memcpy(job.out_error_flags + dst, h_err + src, s.n * sizeof(uint32_t));
+                std::memcpy(job.out_positions + dst * W, h.q + src * W, s.n * W * sizeof(double));
+                if (job.out_collided) std::memcpy(job.out_collided + dst, h.coll + src, s.n);
+                if (job.out_microsteps) std::memcpy(job.out_microsteps + dst, h.micro + src, s.n * sizeof(uint32_t));
+                if (job.out_resolver_iterations) std::memcpy(job.out_resolver_iterations + dst, h.res + src, s.n * sizeof(uint32_t));
+                if (job.out_error_flags) std::memcpy(job.out_error_flags + dst, h.err + src, s.n * sizeof(uint32_t));
             }
             oat += s.n * s.num_legs;
         }
@@ -562,26 +488,19 @@ fks_status fks_multi_check_config_collision(fks_multi_context* m, const double* 
         fks_shard_bounds(n, ndev, g, &lo, &hi);
         const uint64_t k = hi - lo;
         DHIP(d, hipSetDevice(d.device));
-        if (k > d.cap) {
-            DHIP(d, grow(&d.d_starts, k * W));
-            DHIP(d, grow(&d.d_out, k * W));
-            DHIP(d, grow(&d.d_coll, k));
-            DHIP(d, grow(&d.d_micro, k));
-            DHIP(d, grow(&d.d_res, k));
-            DHIP(d, grow(&d.d_err, k));
-            d.cap = k;
-        }
+        fks_buf::ParticleStaging& sg = d.stage;
+        DHIP(d, sg.reserve_rows(k, W));
         if (k == 0) return;
-        DHIP(d, grow_pinned(&d.h_in, &d.cap_h_in, k * W * sizeof(double)));
-        DHIP(d, grow_pinned(&d.h_out, &d.cap_h_out, k * (1 + sizeof(uint32_t))));
-        std::memcpy(d.h_in, configs + lo * W, k * W * sizeof(double));
-        DHIP(d, hipMemcpyAsync(d.d_starts, d.h_in, k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
-        DCTX(d, fks_check_config_collision_device(d.ctx, d.d_starts, k, inflation_ratio, d.d_coll, d.d_err, d.stream, 0),
+        DHIP(d, d.h_in.reserve(k * W * sizeof(double)));
+        DHIP(d, d.h_out.reserve(k * (1 + sizeof(uint32_t))));
+        std::memcpy(d.h_in.get(), configs + lo * W, k * W * sizeof(double));
+        DHIP(d, hipMemcpyAsync(sg.starts.get(), d.h_in.get(), k * W * sizeof(double), hipMemcpyHostToDevice, d.stream));
+        DCTX(d, fks_check_config_collision_device(d.ctx, sg.starts.get(), k, inflation_ratio, sg.coll.get(), sg.err.get(), d.stream, 0),
              "fks_check_config_collision_device");
-        uint32_t* h_err = reinterpret_cast<uint32_t*>(d.h_out);
+        uint32_t* h_err = reinterpret_cast<uint32_t*>(d.h_out.get());
         uint8_t* h_coll = reinterpret_cast<uint8_t*>(h_err + k);
-        DHIP(d, hipMemcpyAsync(h_coll, d.d_coll, k, hipMemcpyDeviceToHost, d.stream));
-        DHIP(d, hipMemcpyAsync(h_err, d.d_err, k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_coll, sg.coll.get(), k, hipMemcpyDeviceToHost, d.stream));
+        DHIP(d, hipMemcpyAsync(h_err, sg.err.get(), k * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
         DHIP(d, hipStreamSynchronize(d.stream));
         std::memcpy(out_collided + lo, h_coll, k);
         if (out_error_flags) std::memcpy(out_error_flags + lo, h_err, k * sizeof(uint32_t));
