@@ -90,7 +90,9 @@ FKS_HD inline void log_twist34(const double* T, double* tw) {
         ax[k] = dsqrt((Rm[k * 4] + 1.0) * 0.5);
         for (int i = 0; i < 3; ++i)
             if (i != k) ax[i] = (Rm[i * 3 + k] + Rm[k * 3 + i]) / (4.0 * ax[k]);
-        w = V3{ax[0] * theta, ax[1] * theta, ax[2] * theta};
+        /* the diagonal fixes the axis up to sign; the skew part, where it is not zero, fixes the sign */
+        const double sg = (dot3(ax[0], ax[1], ax[2], vee.x, vee.y, vee.z) < 0.0) ? -theta : theta;
+        w = V3{ax[0] * sg, ax[1] * sg, ax[2] * sg};
     } else {
         const double f = theta / s;
         w = V3{vee.x * f, vee.y * f, vee.z * f};

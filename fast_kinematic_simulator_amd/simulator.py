@@ -422,6 +422,40 @@ class HipParticleContactSimulator:
         return ({"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
                  "error_flags": errors}, buf)
 
+    def forward_simulate_traced_mutable(self, robot: RobotDescription, start_positions, target_positions, allow_contacts: bool,
+                                        controller_state, step_capacity: Optional[int] = None, config_capacity: int = 4096):
+        """ForwardSimulateMutableRobot with ``enable_tracing = true`` (SPCS:843-919) for a batch
+        (fks_forward_simulate_traced_mutable): forward_simulate_mutable_arrays' controller state,
+        an (n, 2D) float64 array updated in place, plus forward_simulate_traced's trace.
+        Returns (result dict, TraceBuffers)."""
+        self.set_robot(robot)
+        W, D = robot.config_width, robot.num_dofs
+        starts = np.ascontiguousarray(np.asarray(start_positions, dtype=np.float64).reshape(-1, W))
+        targets = np.ascontiguousarray(np.asarray(target_positions, dtype=np.float64).reshape(-1, W))
+        n = starts.shape[0]
+        if n > 0 and targets.shape[0] not in (1, n):
+            raise ValueError("target_positions must hold 1 or len(start_positions) configurations (SPCS:792)")
+        if not (isinstance(controller_state, np.ndarray) and controller_state.dtype == np.float64 and
+                controller_state.flags["C_CONTIGUOUS"] and controller_state.shape == (n, 2 * D)):
+            raise ValueError("controller_state must be a C-contiguous float64 array of shape (n, 2 * num_dofs)")
+        if step_capacity is None:
+            step_capacity = max(1, int(self.solver_config.forward_simulation_time * self.simulation_controller_frequency))
+        buf = TraceBuffers(n, D, W, step_capacity, config_capacity)
+        tr = buf.to_c()
+        out = np.zeros((n, W), dtype=np.float64)
+        collided = np.zeros(n, dtype=np.uint8)
+        micro = np.zeros(n, dtype=np.uint32)
+        resolver = np.zeros(n, dtype=np.uint32)
+        errors = np.zeros(n, dtype=np.uint32)
+        st = self._lib.fks_forward_simulate_traced_mutable(
+            self._ctx, _capi.as_ptr(starts, ctypes.c_double), n, _capi.as_ptr(targets, ctypes.c_double), targets.shape[0],
+            1 if allow_contacts else 0, _capi.as_ptr(controller_state, ctypes.c_double), _capi.as_ptr(out, ctypes.c_double),
+            _capi.as_ptr(collided, ctypes.c_uint8), _capi.as_ptr(micro, ctypes.c_uint32), _capi.as_ptr(resolver, ctypes.c_uint32),
+            _capi.as_ptr(errors, ctypes.c_uint32), ctypes.byref(tr))
+        _capi.check(st, self._ctx, "fks_forward_simulate_traced_mutable")
+        return ({"positions": out, "collided": collided.astype(bool), "microsteps": micro, "resolver_iterations": resolver,
+                 "error_flags": errors}, buf)
+
     def forward_simulate_robot_traced(self, immutable_robot: RobotDescription, start_position, target_position,
                                       allow_contacts: bool):
         """ForwardSimulateRobot(..., trace, enable_tracing=true, ...) (SPCS:824-829):

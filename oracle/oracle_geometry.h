@@ -252,7 +252,9 @@ inline void log_twist(const Iso& T, double twist[6]) {
         ax[k] = fks_math::dsqrt((R[k * 4] + 1.0) * 0.5);
         for (int i = 0; i < 3; ++i)
             if (i != k) ax[i] = (R[i * 3 + k] + R[k * 3 + i]) / (4.0 * ax[k]);
-        w = V3{ax[0] * theta, ax[1] * theta, ax[2] * theta};
+        /* the diagonal fixes the axis up to sign; the skew part, where it is not zero, fixes the sign */
+        const double sg = (((ax[0] * vee.x + ax[1] * vee.y) + ax[2] * vee.z) < 0.0) ? -theta : theta;
+        w = V3{ax[0] * sg, ax[1] * sg, ax[2] * sg};
     } else {
         const double f = theta / s;
         w = V3{vee.x * f, vee.y * f, vee.z * f};
