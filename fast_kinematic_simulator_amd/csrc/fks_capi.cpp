@@ -665,7 +665,11 @@ static fks_status create_impl(const fks_environment* henv, const fks_device_env*
             return FKS_ERR_HIP;
         ctx->has_normals = 1;
     }
-    if (analyzed) {
+    /* the check proof's first arm shows every reachable cell positive, which rules a collision out
+     * only while the threshold -tolerance * res (thr_env) is not above zero: a negative tolerance
+     * makes positive cells below it collide (SPCS:923), so such a simulator evaluates every round */
+    const double thr_env = 0.0 - (params->environment_collision_check_tolerance * ctx->sdf_g.res);
+    if (analyzed && thr_env <= 0.0) {
         ctx->skip_enabled = 1;
         ctx->skip_lplus = lp * (1.0 + 1e-6) + 1e-6;
         ctx->skip_cmax = cm * (1.0 + 1e-6) + 1e-6;
