@@ -12,11 +12,12 @@ import subprocess
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
-SOURCES = ["csrc/fks_kernels.hip", "csrc/fks_capi.cpp", "csrc/fks_batch.cpp", "csrc/fks_multi.cpp", "csrc/fks_env_builder.cpp",
+SOURCES = ["csrc/fks_kernels.hip", "csrc/fks_capi.cpp", "csrc/fks_batch.cpp", "csrc/fks_robot.cpp", "csrc/fks_multi.cpp",
+           "csrc/fks_env_builder.cpp",
            "csrc/fks_env_gpu.hip", "csrc/fks_robot_control.cpp", "csrc/fks_policy_select.cpp", "csrc/fks_cluster.cpp",
            "csrc/fks_specialize.cpp"]
 HEADERS = ["csrc/fks_batch.h", "csrc/fks_buffers.h", "csrc/fks_device.h", "csrc/fks_env_internal.h", "csrc/fks_host_distance.h",
-           "csrc/fks_se3.h", "csrc/fks_specialize.h",
+           "csrc/fks_robot.h", "csrc/fks_se3.h", "csrc/fks_specialize.h",
            "../include/fks_capi.h", "../include/fks_portable_math.h", "../include/fks_control.h"]
 # the kernel source and the headers it includes, carried inside the library for the run-time
 # compilation of shape-specialised kernels (fks_specialize.cpp): name as included -> path
@@ -200,7 +201,10 @@ def build_path_jobs_test(force: bool = False) -> str:
 
 
 PLAN_HEADERS = ("csrc/fks_batch.h", "csrc/fks_device.h", "../include/fks_capi.h", "../include/fks_portable_math.h")
-SELECT_HEADERS = PLAN_HEADERS + ("csrc/fks_host_distance.h", "csrc/fks_se3.h")
+ROBOT_HEADERS = ("csrc/fks_robot.h", "csrc/fks_device.h", "../include/fks_capi.h", "../include/fks_portable_math.h")
+SELECT_HEADERS = PLAN_HEADERS + ("csrc/fks_host_distance.h", "csrc/fks_robot.h", "csrc/fks_se3.h")
+# the host selection and clustering read the dof numbering of csrc/fks_robot.cpp
+SELECT_SOURCES = ("csrc/fks_batch.cpp", "csrc/fks_policy_select.cpp", "csrc/fks_robot.cpp")
 
 
 def _build_host_test(name: str, sources=(), headers=(), force: bool = False) -> str:
@@ -216,7 +220,7 @@ def _build_host_test(name: str, sources=(), headers=(), force: bool = False) -> 
         return target
     rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "include")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-D__HIP_PLATFORM_AMD__",
+           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-pthread", "-D__HIP_PLATFORM_AMD__",
            f"-I{os.path.join(ROOT, 'include')}", f"-I{os.path.join(PKG, 'csrc')}", f"-isystem{rocm_include}", *srcs, "-o", target]
     proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if proc.returncode != 0:
@@ -231,13 +235,18 @@ def build_batch_plan_test(force: bool = False) -> str:
 
 def build_policy_plan_test(force: bool = False) -> str:
     """tests/cpp/policy_plan_test.cpp with the host-only plan of a policy roll-out and the host selection."""
-    return _build_host_test("policy_plan_test", ("csrc/fks_batch.cpp", "csrc/fks_policy_select.cpp"), SELECT_HEADERS, force)
+    return _build_host_test("policy_plan_test", SELECT_SOURCES, SELECT_HEADERS, force)
 
 
 def build_cluster_plan_test(force: bool = False) -> str:
     """tests/cpp/cluster_plan_test.cpp with the host-only plan of a clustering call and the host twin."""
-    return _build_host_test("cluster_plan_test", ("csrc/fks_batch.cpp", "csrc/fks_cluster.cpp", "csrc/fks_policy_select.cpp"),
-                            SELECT_HEADERS, force)
+    return _build_host_test("cluster_plan_test", SELECT_SOURCES + ("csrc/fks_cluster.cpp",), SELECT_HEADERS, force)
+
+
+def build_robot_flatten_test(force: bool = False) -> str:
+    """tests/cpp/robot_flatten_test.cpp with csrc/fks_robot.cpp, the host-only checks, dof numbering, tables and
+    skip-proof constants of a robot description, and the SDF analysis."""
+    return _build_host_test("robot_flatten_test", ("csrc/fks_robot.cpp",), ROBOT_HEADERS, force)
 
 
 def build_buffers_test(force: bool = False) -> str:

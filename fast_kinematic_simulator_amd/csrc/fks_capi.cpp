@@ -19,13 +19,13 @@
 #include <memory>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "fks_capi.h"
 #include "fks_batch.h"
 #include "fks_buffers.h"
 #include "fks_env_internal.h"
+#include "fks_robot.h"
 #include "fks_specialize.h"
 #include "fks_device.h"
 #include "fks_portable_math.h"
@@ -174,21 +174,17 @@ uint32_t forward_steps(double time, double frequency) {
     return steps > 1u ? steps : 1u;
 }
 
-template <typename T>
-hipError_t dev_upload(T** dptr, const T* host, size_t count) {
-    *dptr = nullptr;
-    if (count == 0) return hipSuccess;
-    hipError_t e = hipMalloc((void**)dptr, count * sizeof(T));
-    if (e != hipSuccess) return e;
-    return hipMemcpy(*dptr, host, count * sizeof(T), hipMemcpyHostToDevice);
-}
-
 /* `count` elements of `src` (host or device memory) in a block of `b`'s own */
 template <typename T>
 hipError_t upload(DeviceBuffer<T>& b, const T* src, size_t count, hipMemcpyKind kind = hipMemcpyHostToDevice) {
     const hipError_t e = b.reserve(count);
     if (e != hipSuccess) return e;
     return hipMemcpy(b.get(), src, count * sizeof(T), kind);
+}
+/* a host table in a block of `b`'s own; an empty table takes none (b stays empty, its pointer null) */
+template <typename T>
+hipError_t upload(DeviceBuffer<T>& b, const std::vector<T>& table) {
+    return table.empty() ? hipSuccess : upload(b, table.data(), table.size());
 }
 
 bool valid_grid(const fks_grid_geometry& g) {
@@ -208,55 +204,6 @@ bool same_geometry(const fks_grid_geometry& a, const fks_grid_geometry& b) {
 }
 
 }  // namespace
-
-/* Lipschitz-type constants of the SDF that make a round of points provably free of
- * contact: over axis-neighbour cell pairs, lplus = max |a - b| / res
- * where both values are positive, cmax = max a / res over positive cells with a
- * non-positive neighbour.  For an exact signed EDT both are 1.  Any non-finite value
- * disables skipping. */
-static bool analyze_sdf(const float* v, int64_t nx, int64_t ny, int64_t nz, double res, double* lplus, double* cmax) {
-    const int T = (int)std::max<unsigned>(1u, std::min<unsigned>(16u, std::thread::hardware_concurrency()));
-    std::vector<double> lp(T, 0.0), cm(T, 0.0);
-    std::vector<int> bad(T, 0);
-    std::vector<std::thread> th;
-    const double inv = 1.0 / res;
-    for (int t = 0; t < T; ++t)
-        th.emplace_back([&, t]() {
-            for (int64_t x = t; x < nx; x += T)
-                for (int64_t y = 0; y < ny; ++y)
-                    for (int64_t z = 0; z < nz; ++z) {
-                        const size_t i = ((size_t)x * ny + y) * nz + z;
-                        const double a = v[i];
-                        if (!std::isfinite(a)) {
-                            bad[t] = 1;
-                            continue;
-                        }
-                        const size_t nb[3] = {x + 1 < nx ? i + (size_t)ny * nz : i, y + 1 < ny ? i + (size_t)nz : i,
-                                              z + 1 < nz ? i + 1 : i};
-                        for (int k = 0; k < 3; ++k) {
-                            if (nb[k] == i) continue;
-                            const double b = v[nb[k]];
-                            if (!std::isfinite(b)) continue; /* flagged when visited */
-                            if (a > 0.0 && b > 0.0) {
-                                lp[t] = std::max(lp[t], std::fabs(a - b) * inv);
-                            } else if (a > 0.0) {
-                                cm[t] = std::max(cm[t], a * inv);
-                            } else if (b > 0.0) {
-                                cm[t] = std::max(cm[t], b * inv);
-                            }
-                        }
-                    }
-        });
-    for (auto& h : th) h.join();
-    *lplus = 0.0;
-    *cmax = 0.0;
-    for (int t = 0; t < T; ++t) {
-        if (bad[t]) return false;
-        *lplus = std::max(*lplus, lp[t]);
-        *cmax = std::max(*cmax, cm[t]);
-    }
-    return *lplus > 0.0;
-}
 
 /* One robot shape's module of specialised kernels (fks_specialize.cpp), loaded on the context's
  * device: the plain module (fks_set_specialization) and the batched one of the same shape
@@ -285,6 +232,31 @@ struct ShapedKind {
 static const ShapedKind kPlainModule = {false, "fks_simulate_shaped", "fks_simulate_shaped_small", "fks_check_configs_shaped", "kernel"};
 static const ShapedKind kBatchedModule = {true, "fks_simulate_shaped_pj", "fks_simulate_shaped_pj_small", nullptr, "batch kernel"};
 
+/* the current robot's tables in HBM, one block each (RobotDev points into them): the arrays of
+ * the description and those fks_robot::flatten derives from it */
+struct RobotBuffers {
+    DeviceBuffer<JointDev> joints;
+    DeviceBuffer<int32_t> geom_link;
+    DeviceBuffer<uint32_t> geom_off;
+    DeviceBuffer<double> points;
+    DeviceBuffer<uint16_t> point_geom, point_link;
+    DeviceBuffer<int32_t> dof_joint;
+    DeviceBuffer<uint64_t> link_dof_mask;
+    DeviceBuffer<int32_t> pairs;
+    DeviceBuffer<uint64_t> allowed_mask;
+    DeviceBuffer<double> geom_box, geom_mass;
+    DeviceBuffer<fks_dof_controller> ctrl;
+    DeviceBuffer<double> weights;
+    DeviceBuffer<fksd::RoundDev> rounds;
+    DeviceBuffer<double> dof_lever, dof_lever_box;
+    /* sampled actuators: each sampled dof's two tables, and the SampledDev array that names them */
+    struct SampledTables {
+        DeviceBuffer<double> bounds, samples;
+    };
+    std::vector<SampledTables> sampled_tables;
+    DeviceBuffer<fksd::SampledDev> sampled;
+};
+
 struct fks_context {
     int device = 0;
     std::string last_error;
@@ -306,7 +278,7 @@ struct fks_context {
     /* robot */
     bool has_robot = false;
     RobotDev R;
-    std::vector<void*> robot_allocs;
+    RobotBuffers robot;
     /* launch resources */
     DeviceBuffer<double> d_scratch; /* the persistent grid's per-wave workspaces */
     uint64_t scratch_per_wave = 0;
@@ -393,8 +365,7 @@ static void free_robot(fks_context* ctx) {
     shaped_release(ctx, &ctx->spec); /* a specialised kernel belongs to one robot shape */
     shaped_release(ctx, &ctx->bspec);
     ctx->bspec.pending = false;
-    for (void* p : ctx->robot_allocs) (void)hipFree(p);
-    ctx->robot_allocs.clear();
+    ctx->robot = RobotBuffers();
     ctx->d_scratch.reset();
     ctx->has_robot = false;
 }
@@ -636,8 +607,8 @@ static fks_status create_impl(const fks_environment* henv, const fks_device_env*
         ctx->oob = henv->sdf_oob_value;
         const size_t cells = (size_t)henv->sdf.num_cells[0] * (size_t)henv->sdf.num_cells[1] * (size_t)henv->sdf.num_cells[2];
         if (upload(ctx->d_sdf, henv->sdf_values, cells) != hipSuccess) return FKS_ERR_HIP;
-        analyzed = analyze_sdf(henv->sdf_values, henv->sdf.num_cells[0], henv->sdf.num_cells[1], henv->sdf.num_cells[2],
-                               henv->sdf.resolution, &lp, &cm);
+        analyzed = fks_robot::analyze_sdf(henv->sdf_values, henv->sdf.num_cells[0], henv->sdf.num_cells[1], henv->sdf.num_cells[2],
+                                          henv->sdf.resolution, &lp, &cm);
         /* an initialized grid with no stored entries (every cell empty: a lookup in bounds finds
          * the zero normal, SPCS:219-222) has offsets and may have no entry array */
         if (henv->normal_offsets) {
@@ -860,344 +831,68 @@ fks_status fks_set_robot(fks_context* ctx, const fks_robot_desc* d) {
     if (!d) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "null robot");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->pending && ctx->pending_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->pending_stream));
-    const int G = d->num_geometries;
-    if (G < 1 || G > fksd::kMaxGeoms || !d->geometry_link || !d->geometry_point_offset || !d->points || !d->controllers)
-        return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "robot geometries/controllers missing or more than 64 geometries");
-    const uint32_t P = d->geometry_point_offset[G];
-    if (d->geometry_point_offset[0] != 0 || P < 1 || P > 65535)
-        return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "robot needs 1..65535 points with offsets starting at 0");
-    for (int g = 0; g < G; ++g)
-        if (d->geometry_point_offset[g + 1] < d->geometry_point_offset[g])
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "geometry offsets must be non-decreasing");
-    for (uint32_t i = 0; i < 4 * P; ++i)
-        if (!std::isfinite(d->points[i])) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "non-finite robot point");
-    RobotDev R;
-    std::memset(&R, 0, sizeof(R));
-    R.type = d->robot_type;
-    R.G = G;
-    R.P = (int32_t)P;
-    std::vector<JointDev> joints;
-    std::vector<int32_t> dof_joint;
-    std::vector<int32_t> link_parent_joint;
-    if (d->robot_type == FKS_ROBOT_LINKED) {
-        const int L = d->num_links, J = d->num_joints;
-        if (L < 1 || L > fksd::kMaxLinks || J < 0 || J > fksd::kMaxJoints || (J > 0 && !d->joints))
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "linked robot needs 1..64 links and 0..64 joints");
-        std::vector<int> seen(L, 0);
-        seen[0] = 1;
-        link_parent_joint.assign(L, -1);
-        for (int j = 0; j < J; ++j) {
-            const fks_joint_desc& jd = d->joints[j];
-            if (jd.parent_link < 0 || jd.parent_link >= L || jd.child_link <= 0 || jd.child_link >= L)
-                return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "joint link index out of range");
-            if (!seen[jd.parent_link] || seen[jd.child_link])
-                return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "joints must be in topological order, one parent per link");
-            seen[jd.child_link] = 1;
-            link_parent_joint[jd.child_link] = j;
-            if (jd.type != FKS_JOINT_FIXED && jd.type != FKS_JOINT_REVOLUTE && jd.type != FKS_JOINT_CONTINUOUS &&
-                jd.type != FKS_JOINT_PRISMATIC)
-                return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "unknown joint type");
-            JointDev jv;
-            std::memset(&jv, 0, sizeof(jv));
-            jv.parent = jd.parent_link;
-            jv.child = jd.child_link;
-            jv.type = jd.type;
-            jv.dof = -1;
-            std::memcpy(jv.origin, jd.origin, sizeof(jv.origin));
-            std::memcpy(jv.axis, jd.axis, sizeof(jv.axis));
-            jv.lo = jd.limit_lower;
-            jv.hi = jd.limit_upper;
-            if (jd.type != FKS_JOINT_FIXED) {
-                jv.dof = (int32_t)dof_joint.size();
-                dof_joint.push_back(j);
-            }
-            joints.push_back(jv);
-        }
-        for (int l = 0; l < L; ++l)
-            if (!seen[l]) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "every link must be reached by a joint");
-        if ((int)dof_joint.size() != d->num_dofs || d->num_dofs < 1 || d->num_dofs > fksd::kMaxDofs)
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "num_dofs must equal the number of non-fixed joints (1..64)");
-        for (int g = 0; g < G; ++g)
-            if (d->geometry_link[g] < 0 || d->geometry_link[g] >= L)
-                return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "geometry link index out of range");
-        R.L = L;
-        R.J = J;
-        R.D = d->num_dofs;
-        R.W = d->num_dofs;
-    } else if (d->robot_type == FKS_ROBOT_SE2 || d->robot_type == FKS_ROBOT_SE3) {
-        const int D = (d->robot_type == FKS_ROBOT_SE2) ? 3 : 6;
-        if (d->num_dofs != D || G != 1 || d->geometry_link[0] != 0)
-            return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "SE(2)/SE(3) robots have one geometry on link 0 and 3/6 dofs");
-        R.L = 1;
-        R.J = 0;
-        R.D = D;
-        R.W = (d->robot_type == FKS_ROBOT_SE2) ? 3 : 12;
-    } else {
-        return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "unknown robot type");
-    }
-    std::memcpy(R.base, d->base_transform, sizeof(R.base));
-    /* allowed self-collision masks (CheckIfSelfCollisionAllowed, symmetric, self allowed) */
-    std::vector<uint64_t> allowed(G, 0);
-    for (int g = 0; g < G; ++g) allowed[g] |= 1ull << g;
-    for (int k = 0; k < d->num_allowed_pairs; ++k) {
-        const int a = d->allowed_pairs[2 * k], b = d->allowed_pairs[2 * k + 1];
-        if (a < 0 || a >= G || b < 0 || b >= G) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "allowed pair out of range");
-        allowed[a] |= 1ull << b;
-        allowed[b] |= 1ull << a;
-    }
-    std::vector<int32_t> pairs;
-    for (int a = 0; a < G; ++a)
-        for (int b = a + 1; b < G; ++b)
-            if (!((allowed[a] >> b) & 1ull)) {
-                pairs.push_back(a);
-                pairs.push_back(b);
-            }
-    R.npairs = (int32_t)(pairs.size() / 2);
-    R.self_possible = !(G == 1 || (G == 2 && ((allowed[0] >> 1) & 1ull)));
-    /* per point geometry, per geometry local boxes and link masses (SPCS:1244-1255) */
-    std::vector<uint16_t> point_geom(P), point_link(P);
-    std::vector<double> box(7 * (size_t)G), mass(G);
-    for (int g = 0; g < G; ++g) {
-        const uint32_t b0 = d->geometry_point_offset[g], b1 = d->geometry_point_offset[g + 1];
-        double mn[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, mx[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-        bool w_one = true;
-        for (uint32_t i = b0; i < b1; ++i) {
-            point_geom[i] = (uint16_t)g;
-            point_link[i] = (uint16_t)d->geometry_link[g];
-            for (int a = 0; a < 3; ++a) {
-                mn[a] = std::fmin(mn[a], d->points[4 * i + a]);
-                mx[a] = std::fmax(mx[a], d->points[4 * i + a]);
-            }
-            w_one = w_one && d->points[4 * i + 3] == 1.0;
-        }
-        if (b1 == b0) {
-            for (int a = 0; a < 3; ++a) mn[a] = mx[a] = 0.0;
-        }
-        for (int a = 0; a < 3; ++a) {
-            box[7 * g + a] = 0.5 * (mn[a] + mx[a]);
-            box[7 * g + 3 + a] = 0.5 * (mx[a] - mn[a]);
-        }
-        box[7 * g + 6] = w_one ? 1.0 : 0.0;
-    }
-    /* 64-point rounds of the kernel's lane-strided loops */
-    const int NR = ((int)P + 63) / 64;
-    std::vector<fksd::RoundDev> rounds(NR > 0 ? NR : 1);
-    for (int r = 0; r < NR; ++r) {
-        fksd::RoundDev rd;
-        rd.link = -1;
-        rd.npts = std::min(64, (int)P - 64 * r);
-        rd.radius = 0.0;
-        bool uniform = true;
-        for (int i = 64 * r; i < 64 * r + rd.npts; ++i) {
-            const double* p = d->points + 4 * (size_t)i;
-            uniform = uniform && point_link[i] == point_link[64 * r] && p[3] == 1.0;
-            rd.radius = std::max(rd.radius, std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
-        }
-        if (uniform && std::isfinite(rd.radius)) rd.link = point_link[64 * r];
-        rd.radius = rd.radius * (1.0 + 1e-9) + 1e-12;
-        rounds[r] = rd;
-    }
-    R.nrounds = NR;
-    double previous_link_masses = 0.0;
-    for (int g = G - 1; g >= 0; --g) {
-        const double link_mass = (double)(d->geometry_point_offset[g + 1] - d->geometry_point_offset[g]);
-        mass[g] = link_mass + previous_link_masses;
-        previous_link_masses += link_mass;
-    }
-    /* dofs moving each link: joints whose child is an ancestor-or-self of the link */
-    std::vector<uint64_t> link_mask(R.L, 0);
-    if (d->robot_type == FKS_ROBOT_LINKED) {
-        for (int l = 0; l < R.L; ++l) {
-            int cur = l;
-            while (cur > 0) {
-                const int j = link_parent_joint[cur];
-                if (joints[j].dof >= 0) link_mask[l] |= 1ull << joints[j].dof;
-                cur = joints[j].parent;
-            }
-        }
-    }
-    /* lever arm bound per dof: max over downstream points of (path reach from the
-     * joint frame origin) + |p|; prismatic joints on the path add their largest stroke */
-    std::vector<double> lever(std::max(1, R.D), HUGE_VAL);
-    if (d->robot_type == FKS_ROBOT_LINKED) {
-        bool w_one = true;
-        for (uint32_t i = 0; i < P; ++i) w_one = w_one && d->points[4 * (size_t)i + 3] == 1.0;
-        for (int k = 0; k < R.D && w_one; ++k) {
-            const int jd = dof_joint[k];
-            if (joints[jd].type == FKS_JOINT_PRISMATIC) {
-                const double* ax = joints[jd].axis;
-                lever[k] = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-                continue;
-            }
-            double worst = 0.0;
-            for (int g = 0; g < G; ++g) {
-                const int l = d->geometry_link[g];
-                if (!((link_mask[l] >> k) & 1ull)) continue;
-                /* reach from joint jd's frame origin (= its child link origin) down to link l */
-                double reach = 0.0;
-                for (int cur = l; cur != joints[jd].child;) {
-                    const JointDev& jp = joints[link_parent_joint[cur]];
-                    reach += std::sqrt(jp.origin[3] * jp.origin[3] + jp.origin[7] * jp.origin[7] + jp.origin[11] * jp.origin[11]);
-                    if (jp.type == FKS_JOINT_PRISMATIC)
-                        reach += std::max(std::fabs(jp.lo), std::fabs(jp.hi)) *
-                                 std::sqrt(jp.axis[0] * jp.axis[0] + jp.axis[1] * jp.axis[1] + jp.axis[2] * jp.axis[2]);
-                    cur = jp.parent;
-                }
-                for (uint32_t i = d->geometry_point_offset[g]; i < d->geometry_point_offset[g + 1]; ++i) {
-                    const double* p = d->points + 4 * (size_t)i;
-                    worst = std::max(worst, reach + std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
-                }
-            }
-            const double* ax = joints[jd].axis;
-            const double an = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-            /* AngleAxis with a non-unit axis is not a rotation: no bound */
-            lever[k] = (std::fabs(an - 1.0) < 1e-12 && std::isfinite(worst)) ? worst * (1.0 + 1e-9) + 1e-12 : HUGE_VAL;
-        }
-    } else {
-        /* SE(2) (x, y, theta, applied additively) and SE(3) (body twist v, w: P * exp(twist)):
-         * a point p of the body moves by at most |dt| + |rotation angle| * |p|, the angle at most
-         * the sum of the angular components' magnitudes and |V v| <= |v| (exp's V has operator
-         * norm <= 1), so translation components get lever 1, rotation components max |p| */
-        bool w_one = true;
-        double rmax = 0.0;
-        for (uint32_t i = 0; i < P; ++i) {
-            const double* p = d->points + 4 * (size_t)i;
-            w_one = w_one && p[3] == 1.0;
-            rmax = std::max(rmax, std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
-        }
-        if (w_one && std::isfinite(rmax)) {
-            const int nt = d->robot_type == FKS_ROBOT_SE2 ? 2 : 3; /* translation components first */
-            for (int k = 0; k < R.D; ++k) lever[k] = (k < nt) ? 1.0 + 1e-9 : rmax * (1.0 + 1e-9) + 1e-12;
-        }
-    }
-    /* the same bound over the geometries' local boxes (corner distance <= |centre| + |half
-     * extents|): the self-collision boxes are built from them */
-    std::vector<double> lever_box(std::max(1, R.D), HUGE_VAL);
-    if (d->robot_type == FKS_ROBOT_LINKED) {
-        for (int k = 0; k < R.D; ++k) {
-            const int jd = dof_joint[k];
-            if (joints[jd].type == FKS_JOINT_PRISMATIC) {
-                lever_box[k] = lever[k];
-                continue;
-            }
-            const double* ax = joints[jd].axis;
-            const double an = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-            double worst = 0.0;
-            bool ok = std::fabs(an - 1.0) < 1e-12;
-            for (int g = 0; g < G && ok; ++g) {
-                const int l = d->geometry_link[g];
-                if (!((link_mask[l] >> k) & 1ull)) continue;
-                const double* b = box.data() + 7 * (size_t)g;
-                if (b[6] == 0.0) {
-                    ok = false; /* no box (a point with w != 1): the box test never skips anyway */
-                    break;
-                }
-                double reach = 0.0;
-                for (int cur = l; cur != joints[jd].child;) {
-                    const JointDev& jp = joints[link_parent_joint[cur]];
-                    reach += std::sqrt(jp.origin[3] * jp.origin[3] + jp.origin[7] * jp.origin[7] + jp.origin[11] * jp.origin[11]);
-                    if (jp.type == FKS_JOINT_PRISMATIC)
-                        reach += std::max(std::fabs(jp.lo), std::fabs(jp.hi)) *
-                                 std::sqrt(jp.axis[0] * jp.axis[0] + jp.axis[1] * jp.axis[1] + jp.axis[2] * jp.axis[2]);
-                    cur = jp.parent;
-                }
-                worst = std::max(worst, reach + std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]) +
-                                            std::sqrt(b[3] * b[3] + b[4] * b[4] + b[5] * b[5]));
-            }
-            lever_box[k] = (ok && std::isfinite(worst)) ? worst * (1.0 + 1e-9) + 1e-12 : HUGE_VAL;
-        }
-    }
-    std::vector<double> weights;
-    if (d->robot_type == FKS_ROBOT_LINKED) {
-        for (int k = 0; k < R.D; ++k) weights.push_back(d->distance_weights ? d->distance_weights[k] : 1.0);
-    } else {
-        weights.push_back(d->distance_weights ? d->distance_weights[0] : 1.0);
-        weights.push_back(d->distance_weights ? d->distance_weights[1] : 1.0);
-    }
-    /* SampledUncertainVelocityActuator tables (UNC:123-281), validated before the old robot goes */
-    if (d->sampled_actuators) {
-        for (int k = 0; k < R.D; ++k) {
-            const fks_sampled_actuator& a = d->sampled_actuators[k];
-            if (a.num_bins == 0) continue;
-            if (a.bin_elements == 0 || !a.bin_bounds || !a.bin_samples)
-                return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "sampled actuator needs bounds and >= 1 sample per bin");
-            for (uint64_t i = 0; i < 2ull * a.num_bins; ++i)
-                if (std::isnan(a.bin_bounds[i])) return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "NaN sampled-actuator bin bound");
-            for (uint64_t i = 0; i < (uint64_t)a.num_bins * a.bin_elements; ++i)
-                if (!std::isfinite(a.bin_samples[i]))
-                    return fail(ctx, FKS_ERR_INVALID_ARGUMENT, "non-finite sampled-actuator sample");
-        }
+    fks_robot::Flat flat;
+    {
+        std::string why;
+        const fks_status st = fks_robot::flatten(d, &flat, &why);
+        if (st != FKS_OK) return fail(ctx, st, why); /* the previous robot stays in place */
     }
     free_robot(ctx);
-    auto up = [&](auto** dptr, const auto* host, size_t count) -> hipError_t {
-        hipError_t e = dev_upload(dptr, host, count);
-        if (*dptr) ctx->robot_allocs.push_back((void*)*dptr);
-        return e;
-    };
-    JointDev* dj = nullptr;
-    int32_t *dgl = nullptr, *ddj = nullptr, *dpairs = nullptr;
-    uint32_t* dgo = nullptr;
-    double *dpts = nullptr, *dbox = nullptr, *dmass = nullptr, *dw = nullptr;
-    uint16_t *dpg = nullptr, *dpl = nullptr;
-    uint64_t *dlm = nullptr, *dam = nullptr;
-    fks_dof_controller* dctrl = nullptr;
-    HIP_TRY(ctx, up(&dj, joints.data(), joints.size()));
-    HIP_TRY(ctx, up(&dgl, d->geometry_link, (size_t)G));
-    HIP_TRY(ctx, up(&dgo, d->geometry_point_offset, (size_t)G + 1));
-    HIP_TRY(ctx, up(&dpts, d->points, 4 * (size_t)P));
-    HIP_TRY(ctx, up(&dpg, point_geom.data(), (size_t)P));
-    HIP_TRY(ctx, up(&dpl, point_link.data(), (size_t)P));
-    HIP_TRY(ctx, up(&ddj, dof_joint.data(), dof_joint.size()));
-    HIP_TRY(ctx, up(&dlm, link_mask.data(), link_mask.size()));
-    HIP_TRY(ctx, up(&dpairs, pairs.data(), pairs.size()));
-    HIP_TRY(ctx, up(&dam, allowed.data(), allowed.size()));
-    HIP_TRY(ctx, up(&dbox, box.data(), box.size()));
-    HIP_TRY(ctx, up(&dmass, mass.data(), mass.size()));
-    HIP_TRY(ctx, up(&dctrl, d->controllers, (size_t)R.D));
-    HIP_TRY(ctx, up(&dw, weights.data(), weights.size()));
-    fksd::RoundDev* drounds = nullptr;
-    HIP_TRY(ctx, up(&drounds, rounds.data(), rounds.size()));
-    double* dlever = nullptr;
-    HIP_TRY(ctx, up(&dlever, lever.data(), lever.size()));
-    double* dlever_box = nullptr;
-    HIP_TRY(ctx, up(&dlever_box, lever_box.data(), lever_box.size()));
-    R.joints = dj;
-    R.geom_link = dgl;
-    R.geom_off = dgo;
-    R.points = dpts;
-    R.point_geom = dpg;
-    R.point_link = dpl;
-    R.dof_joint = ddj;
-    R.link_dof_mask = dlm;
-    R.pairs = dpairs;
-    R.allowed_mask = dam;
-    R.geom_box = dbox;
-    R.geom_mass = dmass;
-    R.ctrl = dctrl;
-    R.weights = dw;
-    R.rounds = drounds;
-    R.dof_lever = dlever;
-    R.dof_lever_box = dlever_box;
-    R.sampled_mask = 0;
-    R.sampled = nullptr;
+    RobotBuffers& B = ctx->robot;
+    RobotDev R = flat.R;
+    HIP_TRY(ctx, upload(B.joints, flat.joints));
+    HIP_TRY(ctx, upload(B.geom_link, d->geometry_link, (size_t)R.G));
+    HIP_TRY(ctx, upload(B.geom_off, d->geometry_point_offset, (size_t)R.G + 1));
+    HIP_TRY(ctx, upload(B.points, d->points, 4 * (size_t)R.P));
+    HIP_TRY(ctx, upload(B.point_geom, flat.point_geom));
+    HIP_TRY(ctx, upload(B.point_link, flat.point_link));
+    HIP_TRY(ctx, upload(B.dof_joint, flat.dof_joint));
+    HIP_TRY(ctx, upload(B.link_dof_mask, flat.link_dof_mask));
+    HIP_TRY(ctx, upload(B.pairs, flat.pairs));
+    HIP_TRY(ctx, upload(B.allowed_mask, flat.allowed_mask));
+    HIP_TRY(ctx, upload(B.geom_box, flat.geom_box));
+    HIP_TRY(ctx, upload(B.geom_mass, flat.geom_mass));
+    HIP_TRY(ctx, upload(B.ctrl, d->controllers, (size_t)R.D));
+    HIP_TRY(ctx, upload(B.weights, flat.weights));
+    HIP_TRY(ctx, upload(B.rounds, flat.rounds));
+    HIP_TRY(ctx, upload(B.dof_lever, flat.dof_lever));
+    HIP_TRY(ctx, upload(B.dof_lever_box, flat.dof_lever_box));
+    R.joints = B.joints.get();
+    R.geom_link = B.geom_link.get();
+    R.geom_off = B.geom_off.get();
+    R.points = B.points.get();
+    R.point_geom = B.point_geom.get();
+    R.point_link = B.point_link.get();
+    R.dof_joint = B.dof_joint.get();
+    R.link_dof_mask = B.link_dof_mask.get();
+    R.pairs = B.pairs.get();
+    R.allowed_mask = B.allowed_mask.get();
+    R.geom_box = B.geom_box.get();
+    R.geom_mass = B.geom_mass.get();
+    R.ctrl = B.ctrl.get();
+    R.weights = B.weights.get();
+    R.rounds = B.rounds.get();
+    R.dof_lever = B.dof_lever.get();
+    R.dof_lever_box = B.dof_lever_box.get();
+    /* SampledUncertainVelocityActuator tables (UNC:123-281), checked by flatten */
     if (d->sampled_actuators) {
         std::vector<fksd::SampledDev> sd((size_t)R.D);
         for (int k = 0; k < R.D; ++k) {
             const fks_sampled_actuator& a = d->sampled_actuators[k];
             std::memset(&sd[k], 0, sizeof(sd[k]));
             if (a.num_bins == 0) continue;
-            double *dbounds = nullptr, *dsamples = nullptr;
-            HIP_TRY(ctx, up(&dbounds, a.bin_bounds, 2 * (size_t)a.num_bins));
-            HIP_TRY(ctx, up(&dsamples, a.bin_samples, (size_t)a.num_bins * a.bin_elements));
+            B.sampled_tables.emplace_back();
+            RobotBuffers::SampledTables& t = B.sampled_tables.back();
+            HIP_TRY(ctx, upload(t.bounds, a.bin_bounds, 2 * (size_t)a.num_bins));
+            HIP_TRY(ctx, upload(t.samples, a.bin_samples, (size_t)a.num_bins * a.bin_elements));
             sd[k].nbins = a.num_bins;
             sd[k].elems = a.bin_elements;
-            sd[k].bounds = dbounds;
-            sd[k].samples = dsamples;
+            sd[k].bounds = t.bounds.get();
+            sd[k].samples = t.samples.get();
             R.sampled_mask |= 1ull << k;
         }
-        fksd::SampledDev* dsd = nullptr;
-        HIP_TRY(ctx, up(&dsd, sd.data(), sd.size()));
-        R.sampled = dsd;
+        HIP_TRY(ctx, upload(B.sampled, sd));
+        R.sampled = B.sampled.get();
     }
     {
         const fks_status st = launch_layout(ctx, R);

@@ -79,9 +79,9 @@ void cluster_matrix(const double* M, uint32_t n, double threshold, uint32_t* lab
 extern "C" fks_status fks_cluster_configs(const fks_robot_desc* robot, const double* configs, const uint64_t* group_begin,
                                           uint64_t num_groups, double threshold, double* out_distances, uint32_t* out_labels,
                                           uint32_t* out_num_clusters) {
-    std::vector<fks_host::Dof> dofs;
+    std::vector<fks_robot::Dof> dofs;
     int W = 0;
-    fks_status st = fks_host::robot_shape(robot, &dofs, &W);
+    fks_status st = fks_host::weighted_dofs(robot, &dofs, &W);
     if (st != FKS_OK) return st;
     fks_batch::ClusterPlan plan;
     std::string why;

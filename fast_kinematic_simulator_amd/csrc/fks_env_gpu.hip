@@ -394,7 +394,7 @@ fks_status to_status(hipError_t e) {
     return FKS_ERR_HIP;
 }
 
-/* the host's analyze_sdf (fks_capi.cpp) per cell: lplus = max |a - b| / res over axis
+/* the host's analyze_sdf (fks_robot.cpp) per cell: lplus = max |a - b| / res over axis
  * neighbours both positive, cmax = max positive value / res next to a non-positive
  * one; keys are the doubles' bits (all values >= 0, so bit order is value order) */
 __global__ void env_analyze(const float* __restrict__ sdf, int64_t nx, int64_t ny, int64_t nz, double inv,

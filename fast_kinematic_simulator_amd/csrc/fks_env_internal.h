@@ -43,7 +43,7 @@ struct fks_device_env {
 
 namespace fks_env {
 
-/* the SDF analysis behind the kernels' skip proofs (fks_capi.cpp analyze_sdf) on a
+/* the SDF analysis behind the kernels' skip proofs (fks_robot.cpp analyze_sdf) on a
  * device-resident SDF; false when a value is not finite or the analysis failed */
 bool analyze_sdf_device(const float* d_sdf, int64_t nx, int64_t ny, int64_t nz, double res, double* lplus, double* cmax);
 

@@ -1,5 +1,5 @@
 /*
- * fks_host_distance.h — the robot's shape, ResetPosition and configuration distance on the host,
+ * fks_host_distance.h — the robot's ResetPosition and configuration distance on the host,
  * read from an fks_robot_desc: the one host definition behind fks_policy_select
  * (fks_policy_select.cpp) and fks_cluster_configs (fks_cluster.cpp).
  *
@@ -17,6 +17,7 @@
 
 #include "fks_capi.h"
 #include "fks_portable_math.h"
+#include "fks_robot.h"
 #include "fks_se3.h"
 
 namespace fks_host {
@@ -25,43 +26,18 @@ using fks_math::clamp;
 using fks_math::dabs;
 using fks_math::dsqrt;
 
-struct Dof {
-    bool continuous;
-    double lo, hi;
-};
-
-/* the robot's dofs as fks_set_robot numbers them (linked: its non-fixed joints in joint order)
- * and its flat configuration width */
-inline fks_status robot_shape(const fks_robot_desc* d, std::vector<Dof>* dofs, int* width) {
+/* the dofs and width of a robot that has distance weights; FKS_ERR_INVALID_ARGUMENT for a malformed one */
+inline fks_status weighted_dofs(const fks_robot_desc* d, std::vector<fks_robot::Dof>* dofs, int* width) {
     if (!d || !d->distance_weights) return FKS_ERR_INVALID_ARGUMENT;
-    dofs->clear();
-    if (d->robot_type == FKS_ROBOT_LINKED) {
-        if (d->num_joints < 0 || (d->num_joints > 0 && !d->joints)) return FKS_ERR_INVALID_ARGUMENT;
-        for (int32_t j = 0; j < d->num_joints; ++j) {
-            const fks_joint_desc& jd = d->joints[j];
-            if (jd.type == FKS_JOINT_FIXED) continue;
-            dofs->push_back(Dof{jd.type == FKS_JOINT_CONTINUOUS, jd.limit_lower, jd.limit_upper});
-        }
-        if ((int32_t)dofs->size() != d->num_dofs || d->num_dofs < 1) return FKS_ERR_INVALID_ARGUMENT;
-        *width = d->num_dofs;
-        return FKS_OK;
-    }
-    if (d->robot_type == FKS_ROBOT_SE2 && d->num_dofs == 3) {
-        *width = 3;
-        return FKS_OK;
-    }
-    if (d->robot_type == FKS_ROBOT_SE3 && d->num_dofs == 6) {
-        *width = 12;
-        return FKS_OK;
-    }
-    return FKS_ERR_INVALID_ARGUMENT;
+    return fks_robot::dof_table(d, dofs, width);
 }
 
 /* ResetPosition(q) -> SetPosition: joint limits / angle wrap (the kernel's seg == 0 branch) */
-inline void reset_position(const fks_robot_desc* robot, const std::vector<Dof>& dofs, int W, const double* q, double* p) {
+inline void reset_position(const fks_robot_desc* robot, const std::vector<fks_robot::Dof>& dofs, int W, const double* q, double* p) {
     if (robot->robot_type == FKS_ROBOT_LINKED) {
         for (int k = 0; k < W; ++k)
-            p[k] = dofs[(size_t)k].continuous ? fks_math::wrap_revolute(q[k]) : clamp(q[k], dofs[(size_t)k].lo, dofs[(size_t)k].hi);
+            p[k] = dofs[(size_t)k].type == FKS_JOINT_CONTINUOUS ? fks_math::wrap_revolute(q[k])
+                                                                : clamp(q[k], dofs[(size_t)k].lo, dofs[(size_t)k].hi);
     } else if (robot->robot_type == FKS_ROBOT_SE2) {
         p[0] = q[0];
         p[1] = q[1];
@@ -72,12 +48,12 @@ inline void reset_position(const fks_robot_desc* robot, const std::vector<Dof>& 
 }
 
 /* ComputeConfigurationDistanceTo: config_distance_of<RT> of fks_kernels.hip from cfg to target */
-inline double config_distance(const fks_robot_desc* robot, const std::vector<Dof>& dofs, const double* cfg, const double* target) {
+inline double config_distance(const fks_robot_desc* robot, const std::vector<fks_robot::Dof>& dofs, const double* cfg, const double* target) {
     const double* w = robot->distance_weights;
     if (robot->robot_type == FKS_ROBOT_LINKED) {
         double sum = 0.0;
         for (size_t k = 0; k < dofs.size(); ++k) {
-            const double sd = dofs[k].continuous ? fks_math::wrap_revolute(target[k] - cfg[k]) : target[k] - cfg[k];
+            const double sd = dofs[k].type == FKS_JOINT_CONTINUOUS ? fks_math::wrap_revolute(target[k] - cfg[k]) : target[k] - cfg[k];
             const double d = w[k] * dabs(sd);
             sum = sum + d * d;
         }

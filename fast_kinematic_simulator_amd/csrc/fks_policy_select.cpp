@@ -19,15 +19,15 @@
 #include "fks_host_distance.h"
 
 using fks_host::config_distance;
-using fks_host::Dof;
 using fks_host::reset_position;
-using fks_host::robot_shape;
+using fks_host::weighted_dofs;
+using fks_robot::Dof;
 
 extern "C" fks_status fks_policy_select(const fks_robot_desc* robot, const fks_policy_table* table, const double* configs, uint64_t n,
                                         uint32_t* out_choice, double* out_distance) {
     std::vector<Dof> dofs;
     int W = 0;
-    const fks_status st = robot_shape(robot, &dofs, &W);
+    const fks_status st = weighted_dofs(robot, &dofs, &W);
     if (st != FKS_OK) return st;
     if (!table || !table->keys || !table->targets || table->num_entries == 0 || table->num_entries > FKS_MAX_POLICY_ENTRIES)
         return FKS_ERR_INVALID_ARGUMENT;

@@ -22,6 +22,7 @@
 #include "fks_capi.h"
 #include "fks_control.h"
 #include "fks_portable_math.h"
+#include "fks_robot.h"
 #include "fks_se3.h"
 
 namespace {
@@ -31,36 +32,12 @@ using fks_math::dabs;
 using fks_math::dmax;
 using fks_math::dmin;
 
-struct DofJoint {
-    int32_t type;
-    double lo, hi;
-};
+using fks_robot::Dof;
 
-/* the robot's dofs (linked: its non-fixed joints in joint order, as fks_set_robot numbers
- * them) and its flat configuration width; FKS_ERR_INVALID_ARGUMENT for a malformed robot */
-fks_status robot_dofs(const fks_robot_desc* d, std::vector<DofJoint>* dofs, int* width) {
+/* the dofs and width of a robot that has controllers; FKS_ERR_INVALID_ARGUMENT for a malformed one */
+fks_status controlled_dofs(const fks_robot_desc* d, std::vector<Dof>* dofs, int* width) {
     if (!d || !d->controllers) return FKS_ERR_INVALID_ARGUMENT;
-    dofs->clear();
-    if (d->robot_type == FKS_ROBOT_LINKED) {
-        if (d->num_joints < 0 || (d->num_joints > 0 && !d->joints)) return FKS_ERR_INVALID_ARGUMENT;
-        for (int32_t j = 0; j < d->num_joints; ++j) {
-            const fks_joint_desc& jd = d->joints[j];
-            if (jd.type == FKS_JOINT_FIXED) continue;
-            dofs->push_back(DofJoint{jd.type, jd.limit_lower, jd.limit_upper});
-        }
-        if ((int32_t)dofs->size() != d->num_dofs || d->num_dofs < 1) return FKS_ERR_INVALID_ARGUMENT;
-        *width = d->num_dofs;
-        return FKS_OK;
-    }
-    if (d->robot_type == FKS_ROBOT_SE2 && d->num_dofs == 3) {
-        *width = 3;
-        return FKS_OK;
-    }
-    if (d->robot_type == FKS_ROBOT_SE3 && d->num_dofs == 6) {
-        *width = 12;
-        return FKS_OK;
-    }
-    return FKS_ERR_INVALID_ARGUMENT;
+    return fks_robot::dof_table(d, dofs, width);
 }
 
 bool sampled(const fks_robot_desc* d, int k) {
@@ -71,9 +48,9 @@ bool sampled(const fks_robot_desc* d, int k) {
 
 extern "C" fks_status fks_robot_control_action(const fks_robot_desc* robot, const double* config, const double* target,
                                                double controller_interval, double* pid_state, double* out_control) {
-    std::vector<DofJoint> dofs;
+    std::vector<Dof> dofs;
     int W = 0;
-    const fks_status st = robot_dofs(robot, &dofs, &W);
+    const fks_status st = controlled_dofs(robot, &dofs, &W);
     if (st != FKS_OK) return st;
     if (!config || !target || !pid_state || !out_control) return FKS_ERR_INVALID_ARGUMENT;
     const int D = robot->num_dofs;
@@ -109,9 +86,9 @@ extern "C" fks_status fks_robot_control_action(const fks_robot_desc* robot, cons
 
 extern "C" fks_status fks_robot_apply_control_input(const fks_robot_desc* robot, const double* config, const double* input,
                                                     const double* unit_noise, double* out_config) {
-    std::vector<DofJoint> dofs;
+    std::vector<Dof> dofs;
     int W = 0;
-    const fks_status st = robot_dofs(robot, &dofs, &W);
+    const fks_status st = controlled_dofs(robot, &dofs, &W);
     if (st != FKS_OK) return st;
     if (!config || !input || !out_config) return FKS_ERR_INVALID_ARGUMENT;
     const int D = robot->num_dofs;
@@ -131,7 +108,7 @@ extern "C" fks_status fks_robot_apply_control_input(const fks_robot_desc* robot,
     if (robot->robot_type == FKS_ROBOT_LINKED) {
         /* CopyWithNewValue, then SetPosition's own enforcement (TNUVA:556-565) */
         for (int k = 0; k < D; ++k) {
-            const DofJoint& jd = dofs[(size_t)k];
+            const Dof& jd = dofs[(size_t)k];
             const double raw = config[k] + real[(size_t)k];
             double v;
             if (jd.type == FKS_JOINT_CONTINUOUS) {

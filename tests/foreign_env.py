@@ -7,7 +7,7 @@ derive the other kind from a built environment: both the HIP path (fks_create) a
 oracle go through ``to_c()``, so both see the same struct.
 
 ``lipschitz_constants`` restates the definition of the skip proofs' two SDF constants
-(fks_device.h, fks_capi.cpp analyze_sdf) in NumPy; the tests never ask the library for them.
+(fks_device.h, fks_robot.cpp analyze_sdf) in NumPy; the tests never ask the library for them.
 """
 from __future__ import annotations
 

@@ -14,7 +14,7 @@ import pytest
 
 from fast_kinematic_simulator_amd import workloads as W
 
-from parity_util import assert_counters_identical, assert_identical, mismatch_report, run_both
+from parity_util import COUNTER_KEYS, assert_counters_identical, assert_identical, mismatch_report, run_both
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -146,6 +146,41 @@ def test_specialization_follows_the_robot_and_is_cached(fks_lib, tmp_path, monke
     sim2.set_specialization(True)
     assert sim2.specialization()["from_cache"] and sim2.specialization()["compile_seconds"] == 0.0
     sim2.close()
+
+
+@pytest.mark.gpu
+def test_refused_robot_leaves_the_current_one_in_place(fks_lib):
+    """fks_set_robot checks a description before it releases anything: one it refuses (the
+    telescope's first two joints swapped, so a joint hangs from a link no joint has reached yet)
+    leaves the robot set before it in the context, its tables and its launch layout included, and
+    the same call at the same call index gives the same bytes."""
+    import dataclasses
+
+    import joint_zoo as Z
+    from fast_kinematic_simulator_amd import FksError, _capi, make_linked_simulator
+
+    wl = Z.telescope(8)
+    swapped = dataclasses.replace(wl.robot, joints=[wl.robot.joints[1], wl.robot.joints[0], wl.robot.joints[2]])
+    sim = make_linked_simulator(wl.environment(), wl.solver, wl.controller_frequency, wl.seed)
+    try:
+        sim.set_call_index(3)
+        first = sim.forward_simulate_arrays(wl.robot, wl.starts, wl.targets, True)
+        first_counters, layout = sim.last_call_counters(), sim.launch_info()
+        with pytest.raises(FksError) as refusal:
+            sim.set_robot(swapped)
+        assert refusal.value.status == _capi.ERR_INVALID_ARGUMENT
+        assert str(refusal.value).endswith("fks_set_robot: joints must be in topological order, one parent per link"), refusal.value
+        sim.set_call_index(3)
+        second = sim.forward_simulate_arrays(wl.robot, wl.starts, wl.targets, True)  # the same object: no fks_set_robot
+        second_counters = sim.last_call_counters()
+        assert sim.launch_info() == layout
+    finally:
+        sim.close()
+    assert first["resolver_iterations"].sum() > 0 and first["collided"].any()
+    for k in ("positions", "collided", "microsteps", "resolver_iterations", "error_flags"):
+        assert np.array_equal(first[k], second[k]), k
+    for k in COUNTER_KEYS:
+        assert first_counters[k] == second_counters[k], k
 
 
 @pytest.mark.gpu
