@@ -232,6 +232,21 @@ POLICY_LOST = 0xFFFFFFFE
 POLICY_NONE = 0xFFFFFFFF
 
 
+class ClusterSummary(ctypes.Structure):
+    """fks_cluster_summary: the outputs of a summary call (host or device pointers, as the entry takes them); each may
+    be NULL."""
+    _fields_ = [
+        ("order", c_void_p),
+        ("members", c_void_p),
+        ("count", c_void_p),
+        ("begin", c_void_p),
+        ("expectation", c_void_p),
+        ("variances", c_void_p),
+        ("variance", c_void_p),
+        ("reached", c_void_p),
+    ]
+
+
 class PolicyTable(ctypes.Structure):
     """fks_policy_table: a policy's states (keys), actions (targets) and flags (host or device pointers, as the entry
     takes them) with the two distances of the verdict."""
@@ -374,6 +389,12 @@ PROTOTYPES = [
                                              c_void_p, c_int32]),
     ("fks_cluster_configs_ctx", c_int32, [c_void_p, POINTER(c_double), POINTER(c_uint64), c_uint64, c_double, POINTER(c_double),
                                           POINTER(c_uint32), POINTER(c_uint32)]),
+    ("fks_summarize_clusters", c_int32, [POINTER(RobotDesc), POINTER(c_double), POINTER(c_uint64), c_uint64, POINTER(c_uint32),
+                                         POINTER(c_double), c_double, POINTER(ClusterSummary)]),
+    ("fks_summarize_clusters_device", c_int32, [c_void_p, c_void_p, POINTER(c_uint64), c_uint64, c_void_p, c_void_p, c_double,
+                                                POINTER(ClusterSummary), c_void_p, c_int32]),
+    ("fks_summarize_clusters_ctx", c_int32, [c_void_p, POINTER(c_double), POINTER(c_uint64), c_uint64, POINTER(c_uint32),
+                                             POINTER(c_double), c_double, POINTER(ClusterSummary)]),
     ("fks_forward_simulate_jobs", c_int32, [c_void_p, POINTER(Job), c_uint64]),
     ("fks_forward_simulate_jobs_device", c_int32, [c_void_p, POINTER(Job), c_uint64, c_void_p, c_int32]),
     ("fks_forward_simulate_path_jobs", c_int32, [c_void_p, POINTER(PathJob), c_uint64]),

@@ -15,9 +15,9 @@ ROOT = os.path.dirname(PKG)
 SOURCES = ["csrc/fks_kernels.hip", "csrc/fks_capi.cpp", "csrc/fks_batch.cpp", "csrc/fks_robot.cpp", "csrc/fks_multi.cpp",
            "csrc/fks_env_builder.cpp",
            "csrc/fks_env_gpu.hip", "csrc/fks_robot_control.cpp", "csrc/fks_policy_select.cpp", "csrc/fks_cluster.cpp",
-           "csrc/fks_specialize.cpp"]
+           "csrc/fks_summary.cpp", "csrc/fks_specialize.cpp"]
 HEADERS = ["csrc/fks_batch.h", "csrc/fks_buffers.h", "csrc/fks_device.h", "csrc/fks_env_internal.h", "csrc/fks_host_distance.h",
-           "csrc/fks_robot.h", "csrc/fks_se3.h", "csrc/fks_specialize.h",
+           "csrc/fks_robot.h", "csrc/fks_rotation_mean.h", "csrc/fks_se3.h", "csrc/fks_specialize.h",
            "../include/fks_capi.h", "../include/fks_portable_math.h", "../include/fks_control.h"]
 # the kernel source and the headers it includes, carried inside the library for the run-time
 # compilation of shape-specialised kernels (fks_specialize.cpp): name as included -> path
@@ -243,6 +243,12 @@ def build_cluster_plan_test(force: bool = False) -> str:
     return _build_host_test("cluster_plan_test", SELECT_SOURCES + ("csrc/fks_cluster.cpp",), SELECT_HEADERS, force)
 
 
+def build_summary_plan_test(force: bool = False) -> str:
+    """tests/cpp/summary_plan_test.cpp with the host-only plan of a summary call and the host twin."""
+    return _build_host_test("summary_plan_test", SELECT_SOURCES + ("csrc/fks_summary.cpp",), SELECT_HEADERS + ("csrc/fks_rotation_mean.h",),
+                            force)
+
+
 def build_robot_flatten_test(force: bool = False) -> str:
     """tests/cpp/robot_flatten_test.cpp with csrc/fks_robot.cpp, the host-only checks, dof numbering, tables and
     skip-proof constants of a robot description, and the SDF analysis."""
@@ -273,6 +279,16 @@ def build_cluster_test(force: bool = False, workspace: bool = False) -> str:
         return build_cpp_program(os.path.join("tests", "cpp", "cluster_interface_test.cpp"), "cluster_interface_test_workspace",
                                  force, extra_flags=(f"-I{MOCK_WORKSPACE}",), extra_deps=_headers(MOCK_WORKSPACE))
     return build_cpp_program(os.path.join("tests", "cpp", "cluster_interface_test.cpp"), "cluster_interface_test", force)
+
+
+def build_summary_test(force: bool = False, workspace: bool = False) -> str:
+    """Compile tests/cpp/summary_interface_test.cpp: SummarizeClusters of the plain class and of the
+    planner drop-in against the C-ABI entries on groups read from a file.  workspace=True puts the
+    mock planner workspace on the include path, as build_planner_test."""
+    if workspace:
+        return build_cpp_program(os.path.join("tests", "cpp", "summary_interface_test.cpp"), "summary_interface_test_workspace",
+                                 force, extra_flags=(f"-I{MOCK_WORKSPACE}",), extra_deps=_headers(MOCK_WORKSPACE))
+    return build_cpp_program(os.path.join("tests", "cpp", "summary_interface_test.cpp"), "summary_interface_test", force)
 
 
 def build_shaped_batches_test(force: bool = False) -> str:

@@ -382,4 +382,44 @@ fks_status plan_cluster(ClusterPlan* p, const double* configs, const uint64_t* g
     return FKS_OK;
 }
 
+fks_status plan_summary(SummaryPlan* p, int32_t robot_type, uint32_t width, const double* configs, const uint64_t* group_begin,
+                        uint64_t num_groups, const uint32_t* labels, const double* targets, double reached_distance,
+                        const fks_cluster_summary* out, std::string* why) {
+    *p = SummaryPlan();
+    auto refuse = [&](const char* text) {
+        *why = text;
+        return FKS_ERR_INVALID_ARGUMENT;
+    };
+    if (!out) return refuse("null summary");
+    if (!out->order && !out->members && !out->count && !out->begin && !out->expectation && !out->variances && !out->variance &&
+        !out->reached)
+        return refuse("no output: every pointer of the summary is NULL");
+    if (out->reached && !targets) return refuse("reached is asked for without targets");
+    if (targets && !out->reached) return refuse("targets are given without reached");
+    if (targets && !(reached_distance == reached_distance)) return refuse("reached_distance is NaN");
+    if (num_groups >= kMaxClusterConfigs) return refuse("at most 2^31-1 groups per call");
+    if (num_groups > 0 && !group_begin) return refuse("null group_begin");
+    p->num_groups = num_groups;
+    p->launch = num_groups > 0;
+    p->width = width;
+    p->var_width = fksd::summary_var_width(robot_type, width);
+    p->piece_width = fksd::summary_piece_width(robot_type, width);
+    /* every index the kernels use in a member's row lies inside the row (a row past it is another group's) */
+    if (fksd::summary_row_end(robot_type, width) > p->piece_width) return refuse("internal: a member's terms exceed its workspace row");
+    if (num_groups == 0) return FKS_OK;
+    /* every offset is checked before any is used: nothing is staged before a refusal */
+    for (uint64_t g = 0; g < num_groups; ++g)
+        if (group_begin[g + 1] < group_begin[g]) return refuse("group_begin must be ascending");
+    p->total = group_begin[num_groups];
+    p->first = group_begin[0];
+    if (p->total > kMaxClusterConfigs) return refuse("at most 2^31 configurations per call");
+    for (uint64_t g = 0; g < num_groups; ++g)
+        if (group_begin[g + 1] - group_begin[g] > FKS_MAX_CLUSTER_GROUP)
+            return refuse("a group holds at most FKS_MAX_CLUSTER_GROUP (256) configurations");
+    if (p->total > 0 && !configs) return refuse("null configs");
+    if (p->total > 0 && !labels) return refuse("null labels");
+    p->work_words = p->total * ((uint64_t)p->piece_width + width);
+    return FKS_OK;
+}
+
 }  // namespace fks_batch

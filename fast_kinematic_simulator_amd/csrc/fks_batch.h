@@ -142,6 +142,23 @@ constexpr uint64_t kClusterLdsGroup = 64;
 fks_status plan_cluster(ClusterPlan* p, const double* configs, const uint64_t* group_begin, uint64_t num_groups, double threshold,
                         const void* out_distances, const void* out_labels, const void* out_num_clusters, std::string* why);
 
+/* The plan of a summary call (fks_summarize_clusters and its device entries): the groups' offsets
+ * checked and the widths of the device call's workspace.  group_begin is read only when it is
+ * non-NULL and num_groups > 0, *out only when it is non-NULL; no other pointer is read. */
+struct SummaryPlan {
+    uint64_t num_groups = 0;
+    uint64_t total = 0;        /* N = group_begin[G] */
+    uint64_t first = 0;        /* group_begin[0]: rows below it belong to no group */
+    bool launch = false;       /* false: no group */
+    uint32_t width = 0;        /* W */
+    uint32_t var_width = 0;    /* Wv: W (linked), 3 (SE(2)), 6 (SE(3)) */
+    uint32_t piece_width = 0;  /* doubles of a member's terms in the workspace (fksd::summary_piece_width) */
+    uint64_t work_words = 0;   /* doubles of the device's workspace: N x (piece_width + W) */
+};
+fks_status plan_summary(SummaryPlan* p, int32_t robot_type, uint32_t width, const double* configs, const uint64_t* group_begin,
+                        uint64_t num_groups, const uint32_t* labels, const double* targets, double reached_distance,
+                        const fks_cluster_summary* out, std::string* why);
+
 }  // namespace fks_batch
 
 #endif

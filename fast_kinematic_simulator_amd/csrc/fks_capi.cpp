@@ -79,6 +79,9 @@ extern "C" __global__ void fks_simulate_se3_policy_small(const fksd::SimArgs* ar
 extern "C" __global__ void fks_cluster_linked(const fksd::ClusterArgs args);
 extern "C" __global__ void fks_cluster_se2(const fksd::ClusterArgs args);
 extern "C" __global__ void fks_cluster_se3(const fksd::ClusterArgs args);
+extern "C" __global__ void fks_summary_linked(const fksd::SummaryArgs args);
+extern "C" __global__ void fks_summary_se2(const fksd::SummaryArgs args);
+extern "C" __global__ void fks_summary_se3(const fksd::SummaryArgs args);
 extern "C" __global__ void fks_check_configs_linked(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se2(const fksd::SimArgs* args);
 extern "C" __global__ void fks_check_configs_se3(const fksd::SimArgs* args);
@@ -307,6 +310,13 @@ struct fks_context {
     DeviceBuffer<double> d_cluster_mat;
     DeviceBuffer<uint32_t> d_cluster_labels;
     DeviceBuffer<uint32_t> d_cluster_counts;
+    /* fks_summarize_clusters_device: the staged offsets and the HBM workspace of the members' terms ... */
+    MirroredBuffer<uint64_t> summary_off;
+    DeviceBuffer<double> d_summary_work;
+    /* ... and the host entry's staging: the doubles (configurations, targets, then the outputs) and the words
+     * (labels, then the outputs) */
+    DeviceBuffer<double> d_summary_f64;
+    DeviceBuffer<uint32_t> d_summary_u32;
     MirroredBuffer<fksd::SimArgs> path_args; /* a batch's records (fks_batch::build_records): one per (job, leg) of
                                                 its normal form (a path's legs, a job batch's jobs), then job_first
                                                 and leg_first (SimArgs.job_first) */
@@ -1728,6 +1738,129 @@ fks_status fks_cluster_configs_ctx(fks_context* ctx, const double* configs, cons
     if (d_labels && N > first)
         HIP_TRY(ctx, hipMemcpy(out_labels + first, d_labels + first, (N - first) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (d_counts) HIP_TRY(ctx, hipMemcpy(out_num_clusters, d_counts, G * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return FKS_OK;
+}
+
+/* The summary launch over device buffers: the offsets go up in one pinned copy on the stream, one
+ * workgroup serves a group.  No call index, no counters. */
+static fks_status summary_device(fks_context* ctx, const fks_batch::SummaryPlan& plan, const double* d_configs,
+                                 const uint64_t* group_begin, const uint32_t* d_labels, const double* d_targets,
+                                 double reached_distance, const fks_cluster_summary& d_out, hipStream_t s, int32_t synchronize) {
+    if (!plan.launch) return FKS_OK;
+    const size_t words = (size_t)plan.num_groups + 1;
+    HIP_TRY(ctx, ctx->summary_off.reserve(words));
+    HIP_TRY(ctx, ctx->d_summary_work.reserve((size_t)plan.work_words));
+    /* the previous call has settled, so the pinned copy is free */
+    std::memcpy(ctx->summary_off.host(), group_begin, words * sizeof(uint64_t));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->summary_off.dev(), ctx->summary_off.host(), words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    fksd::SummaryArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.R = ctx->R;
+    a.configs = d_configs;
+    a.offsets = ctx->summary_off.dev();
+    a.labels = d_labels;
+    a.targets = d_targets;
+    a.num_groups = plan.num_groups;
+    a.total = plan.total;
+    a.reached_distance = reached_distance;
+    a.piece_width = plan.piece_width;
+    a.work = ctx->d_summary_work.get();
+    a.out_order = d_out.order;
+    a.out_members = d_out.members;
+    a.out_count = d_out.count;
+    a.out_begin = d_out.begin;
+    a.out_expectation = d_out.expectation;
+    a.out_variances = d_out.variances;
+    a.out_variance = d_out.variance;
+    a.out_reached = d_out.reached;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(plan.num_groups, 1u << 16);
+    void (*kernel)(const fksd::SummaryArgs) =
+        ctx->R.type == FKS_ROBOT_LINKED ? fks_summary_linked : (ctx->R.type == FKS_ROBOT_SE2 ? fks_summary_se2 : fks_summary_se3);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(fksd::kSummaryThreads), 0, s, a);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->pending = true;
+    ctx->pending_kind = 2;
+    ctx->pending_stream = s;
+    if (synchronize) return settle(ctx);
+    return FKS_OK;
+}
+
+/* what both context entries refuse, and the plan of what they run */
+static fks_status summary_entry(fks_context* ctx, fks_batch::SummaryPlan* plan, const double* configs, const uint64_t* group_begin,
+                                uint64_t num_groups, const uint32_t* labels, const double* targets, double reached_distance,
+                                const fks_cluster_summary* out) {
+    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
+    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
+    std::string why;
+    const fks_status st = fks_batch::plan_summary(plan, ctx->R.type, (uint32_t)ctx->R.W, configs, group_begin, num_groups, labels,
+                                                  targets, reached_distance, out, &why);
+    if (st != FKS_OK) return fail(ctx, st, why);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return settle(ctx);
+}
+
+fks_status fks_summarize_clusters_device(fks_context* ctx, const double* d_configs, const uint64_t* group_begin, uint64_t num_groups,
+                                         const uint32_t* d_labels, const double* d_targets, double reached_distance,
+                                         const fks_cluster_summary* d_out, void* stream, int32_t synchronize) {
+    fks_batch::SummaryPlan plan;
+    const fks_status st = summary_entry(ctx, &plan, d_configs, group_begin, num_groups, d_labels, d_targets, reached_distance, d_out);
+    if (st != FKS_OK) return st;
+    return summary_device(ctx, plan, d_configs, group_begin, d_labels, d_targets, reached_distance, *d_out,
+                          reinterpret_cast<hipStream_t>(stream), synchronize);
+}
+
+fks_status fks_summarize_clusters_ctx(fks_context* ctx, const double* configs, const uint64_t* group_begin, uint64_t num_groups,
+                                      const uint32_t* labels, const double* targets, double reached_distance,
+                                      const fks_cluster_summary* out) {
+    fks_batch::SummaryPlan plan;
+    const fks_status st = summary_entry(ctx, &plan, configs, group_begin, num_groups, labels, targets, reached_distance, out);
+    if (st != FKS_OK) return st;
+    if (!plan.launch) return FKS_OK;
+    const size_t W = plan.width, Wv = plan.var_width, N = (size_t)plan.total, G = (size_t)plan.num_groups;
+    /* the doubles: configs [N][W], targets [G][W], then members, expectation [N][W], variances [N][Wv], variance [N] */
+    const size_t f_targets = N * W, f_members = f_targets + (targets ? G * W : 0), f_expect = f_members + (out->members ? N * W : 0),
+                 f_vars = f_expect + (out->expectation ? N * W : 0), f_var = f_vars + (out->variances ? N * Wv : 0),
+                 f_end = f_var + (out->variance ? N : 0);
+    /* the words: labels [N], then order, count, begin, reached [N] */
+    const size_t u_order = N, u_count = u_order + (out->order ? N : 0), u_begin = u_count + (out->count ? N : 0),
+                 u_reached = u_begin + (out->begin ? N : 0), u_end = u_reached + (out->reached ? N : 0);
+    HIP_TRY(ctx, ctx->d_summary_f64.reserve(f_end));
+    HIP_TRY(ctx, ctx->d_summary_u32.reserve(u_end));
+    double* df = ctx->d_summary_f64.get();
+    uint32_t* du = ctx->d_summary_u32.get();
+    fks_cluster_summary d;
+    d.order = out->order ? du + u_order : nullptr;
+    d.count = out->count ? du + u_count : nullptr;
+    d.begin = out->begin ? du + u_begin : nullptr;
+    d.reached = out->reached ? du + u_reached : nullptr;
+    d.members = out->members ? df + f_members : nullptr;
+    d.expectation = out->expectation ? df + f_expect : nullptr;
+    d.variances = out->variances ? df + f_vars : nullptr;
+    d.variance = out->variance ? df + f_var : nullptr;
+    /* rows below group_begin[0] belong to no group: nothing of theirs goes up or comes down */
+    const size_t first = (size_t)plan.first, rows = N - first;
+    if (rows) {
+        HIP_TRY(ctx, hipMemcpy(df + first * W, configs + first * W, rows * W * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(du + first, labels + first, rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (targets && G) HIP_TRY(ctx, hipMemcpy(df + f_targets, targets, G * W * sizeof(double), hipMemcpyHostToDevice));
+    const fks_status run = summary_device(ctx, plan, df, group_begin, du, targets ? df + f_targets : nullptr, reached_distance, d, nullptr, 1);
+    if (run != FKS_OK) return run;
+    if (!rows) return FKS_OK;
+    auto down_f = [&](double* host, const double* dev, size_t width) {
+        return host ? hipMemcpy(host + first * width, dev + first * width, rows * width * sizeof(double), hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    auto down_u = [&](uint32_t* host, const uint32_t* dev) {
+        return host ? hipMemcpy(host + first, dev + first, rows * sizeof(uint32_t), hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIP_TRY(ctx, down_u(out->order, d.order));
+    HIP_TRY(ctx, down_f(out->members, d.members, W));
+    HIP_TRY(ctx, down_u(out->count, d.count));
+    HIP_TRY(ctx, down_u(out->begin, d.begin));
+    HIP_TRY(ctx, down_f(out->expectation, d.expectation, W));
+    HIP_TRY(ctx, down_f(out->variances, d.variances, Wv));
+    HIP_TRY(ctx, down_f(out->variance, d.variance, 1));
+    HIP_TRY(ctx, down_u(out->reached, d.reached));
     return FKS_OK;
 }
 

@@ -453,6 +453,61 @@ struct ClusterArgs {
     double* work;
 };
 
+/* The argument of the summary kernels (fks_summarize_clusters_device, fks_summary_<family>): passed
+ * by value.  offsets is the entry's staged copy of group_begin [G + 1].  work is the context's HBM
+ * workspace: a member's terms at row i (piece_width doubles: first the terms of the expectation's
+ * sums, then the squared differences and the squared distance; an SE(3) cluster's sums lie behind
+ * its row's ten products), then, from N x piece_width on, the expectations [N][W] the second pass
+ * reads.  A workgroup reads and writes the rows of its own group alone, in both parts: every index it
+ * uses in a member's row is below piece_width (summary_row_end, held by fks_batch::plan_summary).
+ * The out pointers are those of fks_cluster_summary, each NULL or [N] rows. */
+constexpr int kSummaryThreads = 256; /* one workgroup per group */
+constexpr int kSummaryProducts = 10; /* an SE(3) member's quaternion products (fks_rotmean::kProducts) */
+constexpr int kSummarySe3Sums = 13;  /* an SE(3) cluster's sums: the ten products and the translation */
+/* where in a member's row the sin of circular component k lies (its cos follows): a linked robot's
+ * dof k at 2 k, the SE(2) angle (its only circular component, k == 2) at 0.  The one definition of
+ * the slot, for the kernels' stores and loads and for summary_row_end below. */
+FKS_HD inline uint32_t summary_term_slot(int32_t robot_type, uint32_t k) { return robot_type == FKS_ROBOT_LINKED ? 2u * k : 0u; }
+#if !defined(__HIPCC_RTC__) /* host-side sizing: the kernels read piece_width from their argument */
+inline uint32_t summary_var_width(int32_t robot_type, uint32_t W) {
+    return robot_type == FKS_ROBOT_LINKED ? W : (robot_type == FKS_ROBOT_SE2 ? 3u : 6u);
+}
+inline uint32_t summary_piece_width(int32_t robot_type, uint32_t W) {
+    if (robot_type == FKS_ROBOT_LINKED) return 2u * W > W + 1u ? 2u * W : W + 1u; /* sin and cos per dof; W squares and the distance */
+    if (robot_type == FKS_ROBOT_SE2) return 4u;                                   /* sin, cos; three squares and the distance */
+    return (uint32_t)(kSummaryProducts + kSummarySe3Sums);                        /* products, sums; six squares and the distance */
+}
+/* one past the highest index of a row that either pass of the kernels touches: fks_batch::plan_summary
+ * holds it to piece_width, so that no workgroup reaches into a row of another group */
+inline uint32_t summary_row_end(int32_t robot_type, uint32_t W) {
+    const uint32_t spread = summary_var_width(robot_type, W) + 1u; /* the squares, then the squared distance */
+    uint32_t terms = (uint32_t)(kSummaryProducts + kSummarySe3Sums);
+    if (robot_type == FKS_ROBOT_LINKED) terms = W ? summary_term_slot(robot_type, W - 1u) + 2u : 0u;
+    if (robot_type == FKS_ROBOT_SE2) terms = summary_term_slot(robot_type, 2u) + 2u;
+    return terms > spread ? terms : spread;
+}
+#endif
+struct SummaryArgs {
+    RobotDev R;
+    const double* configs;
+    const uint64_t* offsets;
+    const uint32_t* labels;
+    const double* targets; /* [G][W] or NULL */
+    uint64_t num_groups;
+    uint64_t total; /* N */
+    double reached_distance;
+    uint32_t piece_width;
+    double* work;
+    uint32_t* out_order;
+    double* out_members;
+    uint32_t* out_count;
+    uint32_t* out_begin;
+    double* out_expectation;
+    double* out_variances;
+    double* out_variance;
+    uint32_t* out_reached;
+};
+
 enum {
     kCntSuccessful = 0,
     kCntUnsuccessful,

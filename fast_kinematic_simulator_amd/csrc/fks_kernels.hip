@@ -4781,6 +4781,7 @@ extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_policy_small(
 #endif /* FKS_SHAPE_L */
 
 #if !defined(FKS_SHAPE_L)
+#include "fks_rotation_mean.h" /* the summary kernels' alone: a shape-specialised build never opens it */
 /* Outcome clustering (fks_cluster_configs_device; the host twin is fks_cluster_configs, the
  * definition is in fks_capi.h): one workgroup of kClusterThreads per group, groups strided over
  * the grid.
@@ -4956,6 +4957,263 @@ extern "C" __global__ void __launch_bounds__(kClusterThreads) fks_cluster_se2(co
 }
 extern "C" __global__ void __launch_bounds__(kClusterThreads) fks_cluster_se3(const ClusterArgs args) {
     cluster_groups<FKS_ROBOT_SE3>(args);
+}
+
+/* Cluster summaries (fks_summarize_clusters_device; the host twin is fks_summarize_clusters, the
+ * definition is in fks_capi.h): one workgroup of kSummaryThreads per group, groups strided over
+ * the grid; a group holds at most FKS_MAX_CLUSTER_GROUP = kSummaryThreads configurations.
+ *   regroup  the labels are read once into LDS; an integer histogram, thread c's exclusive prefix,
+ *            and thread i's stable rank (its cluster's begin plus the j < i of the same label; the
+ *            configurations of no cluster behind all clusters) give order, members, count, begin.
+ *   terms    the transcendental part is member-parallel: sin and cos of every circular component,
+ *            an SE(3) member's quaternion and its ten products, go to the member's row of the
+ *            context's workspace (fksd::SummaryArgs).
+ *   sums     one thread per (cluster, component) adds its members' terms in ascending member
+ *            order from +0.0, the twin's order, at most 256 additions; one thread per SE(3)
+ *            cluster runs the Jacobi iteration (fks_rotation_mean.h).  The expectations go to the
+ *            workspace (a group of 256 wide configurations does not fit LDS beside the staged
+ *            configurations) and to the caller.
+ *   spread   the same again: squared differences or twists and the squared distance per member,
+ *            then the serial sums; reached is an integer LDS counter per cluster.
+ * The workspace is written and read by one workgroup between barriers, as cluster_groups' links. */
+template <int RT>
+__device__ __forceinline__ bool summary_circular(const JointDev* joints, const int32_t* dofj, uint32_t k) {
+    if constexpr (RT == FKS_ROBOT_LINKED) return joints[dofj[k]].type == FKS_JOINT_CONTINUOUS;
+    return RT == FKS_ROBOT_SE2 && k == 2;
+}
+template <int RT>
+__device__ __forceinline__ void summarize_groups(const SummaryArgs& A) {
+    constexpr uint32_t NT = kSummaryThreads, MAXN = FKS_MAX_CLUSTER_GROUP;
+    constexpr uint32_t NP = kSummaryProducts, NS = kSummarySe3Sums;
+    static_assert(NP == (uint32_t)fks_rotmean::kProducts, "the products of fks_rotation_mean.h");
+    __shared__ double s_cfg[kClusterLdsConfigs];
+    __shared__ double s_joints[kJointWords * kMaxJoints];
+    __shared__ int32_t s_dofj[kMaxDofs];
+    __shared__ uint32_t s_label[MAXN], s_count[MAXN], s_begin[MAXN], s_order[MAXN], s_reached[MAXN];
+    const RobotDev& R = A.R;
+    const uint32_t W = (uint32_t)R.W, P = A.piece_width;
+    const uint32_t Wv = (RT == FKS_ROBOT_LINKED) ? W : (RT == FKS_ROBOT_SE2 ? 3u : 6u);
+    const uint32_t tid = threadIdx.x;
+    const JointDev* joints = R.joints;
+    const int32_t* dofj = R.dof_joint;
+    if constexpr (RT == FKS_ROBOT_LINKED) {
+        /* the robot tables the distance and the circular test read, once per workgroup */
+        if (R.J <= kMaxJoints && R.D <= kMaxDofs) {
+            const double* sj = reinterpret_cast<const double*>(R.joints);
+            for (uint32_t k = tid; k < (uint32_t)(R.J * kJointWords); k += NT) s_joints[k] = gp(sj)[k];
+            for (uint32_t k = tid; k < (uint32_t)R.D; k += NT) s_dofj[k] = gp(R.dof_joint)[k];
+            joints = reinterpret_cast<const JointDev*>(s_joints);
+            dofj = s_dofj;
+        }
+    }
+    const bool want_mean = A.out_expectation || A.out_variances || A.out_variance;
+    const bool want_spread = A.out_variances || A.out_variance;
+    const uint64_t G = A.num_groups;
+    const FKS_GLOBAL uint64_t* gb = gp(A.offsets);
+    /* the expectations [N][W] behind the members' terms.  A workgroup touches the rows of its own group
+     * alone, in both parts of the workspace: rows [first, first + n) of the terms (every index below P,
+     * fksd::summary_row_end) and of Ew; no row is shared between groups */
+    double* const Ew = A.work + A.total * (uint64_t)P;
+    for (uint64_t g = blockIdx.x; g < G; g += gridDim.x) {
+        const uint64_t first = gb[g];
+        const uint32_t n = (uint32_t)(gb[g + 1] - first); /* <= MAXN (fks_batch::plan_summary) */
+        const double* C = A.configs + first * W;
+        if (n * W <= (uint32_t)kClusterLdsConfigs) {
+            for (uint32_t k = tid; k < n * W; k += NT) s_cfg[k] = gp(C)[k];
+            C = s_cfg;
+        }
+        for (uint32_t k = tid; k < n; k += NT) {
+            s_label[k] = gp(A.labels)[first + k];
+            s_count[k] = 0u;
+            s_reached[k] = 0u;
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < n; i += NT) {
+            const uint32_t l = s_label[i];
+            if (l < n) atomicAdd(&s_count[l], 1u);
+        }
+        __syncthreads();
+        for (uint32_t c = tid; c < n; c += NT) {
+            uint32_t b = 0;
+            for (uint32_t q = 0; q < c; ++q) b += s_count[q];
+            s_begin[c] = b;
+        }
+        __syncthreads();
+        const uint32_t placed = n ? s_begin[n - 1] + s_count[n - 1] : 0u; /* the members of all clusters */
+        for (uint32_t i = tid; i < n; i += NT) {
+            const uint32_t l = s_label[i];
+            const bool in = l < n;
+            uint32_t pos = in ? s_begin[l] : placed;
+            for (uint32_t j = 0; j < i; ++j) {
+                const uint32_t lj = s_label[j];
+                pos += (in ? lj == l : lj >= n) ? 1u : 0u;
+            }
+            s_order[pos] = i; /* pos < n: a permutation of the group */
+        }
+        __syncthreads();
+        for (uint32_t k = tid; k < n; k += NT) {
+            if (A.out_order) gpw(A.out_order)[first + k] = (uint32_t)first + s_order[k];
+            if (A.out_count) gpw(A.out_count)[first + k] = s_count[k];
+            if (A.out_begin) gpw(A.out_begin)[first + k] = (uint32_t)first + s_begin[k];
+        }
+        if (A.out_members)
+            for (uint32_t t = tid; t < n * W; t += NT) {
+                const uint32_t k = t / W, w = t - k * W;
+                gpw(A.out_members)[(first + k) * W + w] = C[s_order[k] * W + w];
+            }
+        if (want_mean) {
+            /* terms of the expectation's sums, member-parallel */
+            if constexpr (RT == FKS_ROBOT_SE3) {
+                for (uint32_t i = tid; i < n; i += NT) {
+                    if (s_label[i] >= n) continue;
+                    double T[12], q[4], p[NP];
+                    for (int k = 0; k < 12; ++k) T[k] = C[i * W + k];
+                    fks_rotmean::quat_of_rotation34(T, q);
+                    fks_rotmean::quat_products(q, p);
+                    FKS_GLOBAL double* row = gpw(A.work) + (first + i) * P;
+                    for (uint32_t a = 0; a < NP; ++a) row[a] = p[a];
+                }
+            } else {
+                for (uint32_t t = tid; t < n * W; t += NT) {
+                    const uint32_t i = t / W, k = t - i * W;
+                    if (s_label[i] >= n || !summary_circular<RT>(joints, dofj, k)) continue;
+                    const double a = C[i * W + k];
+                    FKS_GLOBAL double* row = gpw(A.work) + (first + i) * P;
+                    const uint32_t slot = summary_term_slot(RT, k); /* inside the member's own row (fks_device.h) */
+                    row[slot] = fks_math::sin(a);
+                    row[slot + 1] = fks_math::cos(a);
+                }
+            }
+            __syncthreads();
+            if constexpr (RT == FKS_ROBOT_SE3) {
+                for (uint32_t t = tid; t < n * NS; t += NT) {
+                    const uint32_t c = t / NS, a = t - c * NS;
+                    const uint32_t m = s_count[c], b = s_begin[c];
+                    double sum = 0.0;
+                    for (uint32_t j = 0; j < m; ++j) {
+                        const uint32_t i = s_order[b + j];
+                        sum = sum + (a < NP ? gp(A.work)[(first + i) * P + a] : C[i * W + 4 * (a - NP) + 3]);
+                    }
+                    gpw(A.work)[(first + c) * P + NP + a] = sum;
+                }
+                __syncthreads();
+                for (uint32_t c = tid; c < n; c += NT) {
+                    const uint32_t m = s_count[c];
+                    double E[12];
+                    for (int k = 0; k < 12; ++k) E[k] = 0.0;
+                    if (m > 0) {
+                        const FKS_GLOBAL double* sums = gp(A.work) + (first + c) * P + NP;
+                        double S[NP], q[4];
+                        for (uint32_t a = 0; a < NP; ++a) S[a] = sums[a];
+                        fks_rotmean::dominant_eigenvector4(S, q);
+                        fks_rotmean::rotation34_of_quat(q, E);
+                        const double dm = (double)m;
+                        E[3] = sums[NP] / dm;
+                        E[7] = sums[NP + 1] / dm;
+                        E[11] = sums[NP + 2] / dm;
+                    }
+                    for (int k = 0; k < 12; ++k) {
+                        gpw(Ew)[(first + c) * W + k] = E[k];
+                        if (A.out_expectation) gpw(A.out_expectation)[(first + c) * W + k] = E[k];
+                    }
+                }
+            } else {
+                for (uint32_t t = tid; t < n * W; t += NT) {
+                    const uint32_t c = t / W, k = t - c * W;
+                    const uint32_t m = s_count[c], b = s_begin[c];
+                    double e = 0.0;
+                    if (m > 0) {
+                        if (summary_circular<RT>(joints, dofj, k)) {
+                            double ss = 0.0, sc = 0.0;
+                            for (uint32_t j = 0; j < m; ++j) {
+                                const FKS_GLOBAL double* row = gp(A.work) + (first + s_order[b + j]) * P;
+                                ss = ss + row[summary_term_slot(RT, k)];
+                                sc = sc + row[summary_term_slot(RT, k) + 1];
+                            }
+                            e = fks_math::atan2(ss, sc);
+                        } else {
+                            double sum = 0.0;
+                            for (uint32_t j = 0; j < m; ++j) sum = sum + C[s_order[b + j] * W + k];
+                            e = sum / (double)m;
+                        }
+                    }
+                    gpw(Ew)[(first + c) * W + k] = e;
+                    if (A.out_expectation) gpw(A.out_expectation)[(first + c) * W + k] = e;
+                }
+            }
+            __syncthreads();
+        }
+        if (want_spread) {
+            /* squared differences from the expectation to each member, member-parallel */
+            if constexpr (RT == FKS_ROBOT_SE3) {
+                for (uint32_t i = tid; i < n; i += NT) {
+                    const uint32_t l = s_label[i];
+                    if (l >= n) continue;
+                    double E[12], T[12], Ei[12], Dm[12], tw[6];
+                    for (int k = 0; k < 12; ++k) {
+                        E[k] = gp(Ew)[(first + l) * W + k];
+                        T[k] = C[i * W + k];
+                    }
+                    inverse34(E, Ei);
+                    compose34(Ei, T, Dm);
+                    log_twist34(Dm, tw);
+                    FKS_GLOBAL double* row = gpw(A.work) + (first + i) * P;
+                    for (int k = 0; k < 6; ++k) row[k] = tw[k] * tw[k];
+                }
+            } else {
+                for (uint32_t t = tid; t < n * W; t += NT) {
+                    const uint32_t i = t / W, k = t - i * W;
+                    const uint32_t l = s_label[i];
+                    if (l >= n) continue;
+                    const double raw = C[i * W + k] - gp(Ew)[(first + l) * W + k];
+                    const double d = summary_circular<RT>(joints, dofj, k) ? fks_math::wrap_revolute(raw) : raw;
+                    gpw(A.work)[(first + i) * P + k] = d * d;
+                }
+            }
+            for (uint32_t i = tid; i < n; i += NT) {
+                const uint32_t l = s_label[i];
+                if (l >= n) continue;
+                const double dist = config_distance_of<RT>(R, joints, dofj, Ew + (first + l) * W, C + (size_t)i * W);
+                gpw(A.work)[(first + i) * P + Wv] = dist * dist;
+            }
+        }
+        if (A.targets && A.out_reached)
+            for (uint32_t i = tid; i < n; i += NT) {
+                const uint32_t l = s_label[i];
+                if (l >= n) continue;
+                const double dist = config_distance_of<RT>(R, joints, dofj, C + (size_t)i * W, A.targets + g * W);
+                if (dist < A.reached_distance) atomicAdd(&s_reached[l], 1u);
+            }
+        __syncthreads();
+        if (want_spread)
+            for (uint32_t t = tid; t < n * (Wv + 1); t += NT) {
+                const uint32_t c = t / (Wv + 1), a = t - c * (Wv + 1);
+                const uint32_t m = s_count[c], b = s_begin[c];
+                double v = 0.0;
+                if (m > 0) {
+                    double sum = 0.0;
+                    for (uint32_t j = 0; j < m; ++j) sum = sum + gp(A.work)[(first + s_order[b + j]) * P + a];
+                    v = sum / (double)m;
+                }
+                if (a < Wv) {
+                    if (A.out_variances) gpw(A.out_variances)[(first + c) * Wv + a] = v;
+                } else if (A.out_variance) {
+                    gpw(A.out_variance)[first + c] = v;
+                }
+            }
+        if (A.out_reached)
+            for (uint32_t c = tid; c < n; c += NT) gpw(A.out_reached)[first + c] = s_reached[c];
+        __syncthreads(); /* the next group reuses the LDS arrays */
+    }
+}
+extern "C" __global__ void __launch_bounds__(kSummaryThreads) fks_summary_linked(const SummaryArgs args) {
+    summarize_groups<FKS_ROBOT_LINKED>(args);
+}
+extern "C" __global__ void __launch_bounds__(kSummaryThreads) fks_summary_se2(const SummaryArgs args) {
+    summarize_groups<FKS_ROBOT_SE2>(args);
+}
+extern "C" __global__ void __launch_bounds__(kSummaryThreads) fks_summary_se3(const SummaryArgs args) {
+    summarize_groups<FKS_ROBOT_SE3>(args);
 }
 
 /* device self-test of the portable libm (fks_selftest_math) */

@@ -19,6 +19,9 @@ from .environment import DeviceEnvironment, SimulatorEnvironment
 from .robots import RobotDescription
 from .trace import ForwardSimulationStepTrace, TraceBuffers
 
+# the outputs of a summary call, in the order of fks_cluster_summary
+SUMMARY_OUTPUTS = ("order", "members", "count", "begin", "expectation", "variances", "variance", "reached")
+
 
 @dataclass
 class SimulatorSolverParameters:
@@ -726,6 +729,89 @@ class HipParticleContactSimulator:
             ctypes.c_void_p(d_out_distances or None), ctypes.c_void_p(d_out_labels or None),
             ctypes.c_void_p(d_out_num_clusters or None), ctypes.c_void_p(stream or None), 1 if synchronize else 0)
         _capi.check(st, self._ctx, "fks_cluster_configs_device")
+
+    def summarize_clusters(self, robot: RobotDescription, groups, labels, targets=None, reached_distance: float = 0.0,
+                           outputs=None) -> dict:
+        """fks_summarize_clusters_ctx: every cluster of every group as a child state, in one launch
+        (include/fks_capi.h).  groups and labels are sequences of (n_g, W) and (n_g,) arrays, as
+        cluster_outcomes takes and returns them; targets (G, W) or None.  Returns the arrays named in
+        `outputs` (None: all of SUMMARY_OUTPUTS, "reached" only with targets), each with N rows, and
+        "group_begin"."""
+        self.set_robot(robot)
+        call = _SummaryCall(robot, groups, labels, targets, outputs)
+        st = self._lib.fks_summarize_clusters_ctx(self._ctx, *call.inputs(), float(reached_distance), ctypes.byref(call.struct))
+        _capi.check(st, self._ctx, "fks_summarize_clusters_ctx")
+        return call.result()
+
+    def summarize_clusters_device(self, robot: RobotDescription, d_configs, group_begin, d_labels, d_targets=0,
+                                  reached_distance: float = 0.0, d_out=None, stream=0, synchronize=False):
+        """fks_summarize_clusters_device: d_configs and d_labels are device pointers (int), e.g. the
+        buffers a jobs call and a clustering call wrote; group_begin the G + 1 ascending offsets (a
+        host sequence); d_targets a device pointer to (G, W) doubles or 0; d_out a dict of device
+        pointers by output name (SUMMARY_OUTPUTS; absent or 0: not asked for), each of N rows."""
+        self.set_robot(robot)
+        begin = np.ascontiguousarray(np.asarray(group_begin, dtype=np.uint64).reshape(-1))
+        if begin.size == 0:
+            begin = np.zeros(1, dtype=np.uint64)
+        d_out = d_out or {}
+        unknown = set(d_out) - set(SUMMARY_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown summary outputs {sorted(unknown)}")
+        struct = _capi.ClusterSummary(**{name: (d_out.get(name) or None) for name in SUMMARY_OUTPUTS})
+        st = self._lib.fks_summarize_clusters_device(
+            self._ctx, ctypes.c_void_p(d_configs or None), _capi.as_ptr(begin, ctypes.c_uint64), begin.size - 1,
+            ctypes.c_void_p(d_labels or None), ctypes.c_void_p(d_targets or None), float(reached_distance), ctypes.byref(struct),
+            ctypes.c_void_p(stream or None), 1 if synchronize else 0)
+        _capi.check(st, self._ctx, "fks_summarize_clusters_device")
+
+
+class _SummaryCall:
+    """the host arrays of one summary call: inputs, the outputs asked for and the struct that names them"""
+
+    def __init__(self, robot, groups, labels, targets, outputs):
+        W = robot.config_width
+        self.configs, self.begin = _cluster_groups(groups, W)
+        N, G = int(self.begin[-1]), len(self.begin) - 1
+        lab = [np.asarray(l, dtype=np.uint32).reshape(-1) for l in labels]
+        if [l.size for l in lab] != [int(v) for v in np.diff(self.begin)]:
+            raise ValueError("labels must hold one array per group, of the group's length")
+        self.labels = np.ascontiguousarray(np.concatenate(lab)) if lab else np.zeros(0, dtype=np.uint32)
+        self.targets = None if targets is None else np.ascontiguousarray(np.asarray(targets, dtype=np.float64).reshape(G, W))
+        Wv = W if robot.robot_type == _capi.ROBOT_LINKED else (3 if robot.robot_type == _capi.ROBOT_SE2 else 6)
+        shapes = {"order": ((N,), np.uint32), "members": ((N, W), np.float64), "count": ((N,), np.uint32), "begin": ((N,), np.uint32),
+                  "expectation": ((N, W), np.float64), "variances": ((N, Wv), np.float64), "variance": ((N,), np.float64),
+                  "reached": ((N,), np.uint32)}
+        if outputs is None:
+            outputs = [n for n in SUMMARY_OUTPUTS if n != "reached" or self.targets is not None]
+        unknown = set(outputs) - set(shapes)
+        if unknown:
+            raise ValueError(f"unknown summary outputs {sorted(unknown)}")
+        names = [n for n in SUMMARY_OUTPUTS if n in outputs]
+        # one spare element keeps a pointer non-NULL for N == 0
+        self.flat = {n: np.zeros(int(np.prod(shapes[n][0])) + 1, dtype=shapes[n][1]) for n in names}
+        self.shapes = {n: shapes[n][0] for n in names}
+        self.struct = _capi.ClusterSummary(**{n: self.flat[n].ctypes.data for n in names})
+
+    def inputs(self):
+        return (_cluster_ptr(self.configs, ctypes.c_double), _capi.as_ptr(self.begin, ctypes.c_uint64), len(self.begin) - 1,
+                _cluster_ptr(self.labels, ctypes.c_uint32), _cluster_ptr(self.targets, ctypes.c_double))
+
+    def result(self) -> dict:
+        out = {n: a[:-1].reshape(self.shapes[n]).copy() for n, a in self.flat.items()}
+        out["group_begin"] = self.begin.copy()
+        return out
+
+
+def summarize_clusters_host(robot: RobotDescription, groups, labels, targets=None, reached_distance: float = 0.0,
+                            outputs=None) -> dict:
+    """fks_summarize_clusters: the host twin of Simulator.summarize_clusters, with the kernels'
+    arithmetic and without a context or a GPU; the same result byte for byte."""
+    call = _SummaryCall(robot, groups, labels, targets, outputs)
+    desc, keep = robot.to_c()
+    st = _capi.lib().fks_summarize_clusters(ctypes.byref(desc), *call.inputs(), float(reached_distance), ctypes.byref(call.struct))
+    del keep
+    _capi.check(st, None, "fks_summarize_clusters")
+    return call.result()
 
 
 def _cluster_groups(groups, W: int):

@@ -198,6 +198,14 @@ class DeviceSet {
               ctx_, what);
     }
 
+    /* every cluster of every group as a child state in one launch (fks_summarize_clusters_ctx,
+     * host buffers, its arguments): on devices[0] alone, as cluster_configs, and like it no batch
+     * of the simulation */
+    void summarize_clusters(const double* configs, const uint64_t* group_begin, uint64_t num_groups, const uint32_t* labels,
+                            const double* targets, double reached_distance, const fks_cluster_summary* out, const char* what) {
+        Check(fks_summarize_clusters_ctx(ctx_, configs, group_begin, num_groups, labels, targets, reached_distance, out), ctx_, what);
+    }
+
     /* many independent calls in one launch per device (fks_forward_simulate_jobs, host
      * buffers); the devices are chosen from the jobs' particles together as for simulate() */
     void simulate_jobs(const fks_job* jobs, uint64_t num_jobs, const char* what) {

@@ -385,6 +385,39 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
         return fks::HipParticleContactSimulator::ClusterOutcomesHost(robot.HipDescription(), FlatGroups(robot, groups), threshold,
                                                                      want_distances);
     }
+    /* Not part of SimulatorInterface: the planner's step after the clustering
+     * (fks_summarize_clusters_ctx).  Every cluster of every group becomes a child state: its
+     * regrouped members, their expectation, per-dimension and scalar variances and, with one
+     * target per group, the members within reached_distance of it, in one launch on devices[0].
+     * The rows are flat configurations (ToFlat / FromFlat).  No call index is consumed. */
+    fks::ClusterSummaries SummarizeClusters(const std::shared_ptr<BaseRobotType>& immutable_robot,
+                                            const std::vector<std::vector<Configuration, ConfigAlloc>>& groups,
+                                            const std::vector<std::vector<uint32_t>>& labels,
+                                            const std::vector<Configuration, ConfigAlloc>& targets = {}, const double reached_distance = 0.0) {
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        SetRobot(robot);
+        const size_t W = (size_t)robot.HipDescription().ConfigurationWidth();
+        fks::FlatSummaryGroups flat(FlatGroups(robot, groups), labels, FlatTargets(robot, targets), W,
+                                    fks::SummaryVarianceWidth(robot.HipDescription().View(), W));
+        dev_->summarize_clusters(flat.configs.data(), flat.out.group_begin.data(), flat.num_groups(), flat.labels.data(),
+                                 flat.targets_or_null(), reached_distance, &flat.summary, "SummarizeClusters");
+        return std::move(flat.out);
+    }
+    /* fks_summarize_clusters on the host, without a simulator: the same result byte for byte */
+    static fks::ClusterSummaries SummarizeClustersHost(const std::shared_ptr<BaseRobotType>& immutable_robot,
+                                                       const std::vector<std::vector<Configuration, ConfigAlloc>>& groups,
+                                                       const std::vector<std::vector<uint32_t>>& labels,
+                                                       const std::vector<Configuration, ConfigAlloc>& targets = {},
+                                                       const double reached_distance = 0.0) {
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        return fks::HipParticleContactSimulator::SummarizeClustersHost(robot.HipDescription(), FlatGroups(robot, groups), labels,
+                                                                       FlatTargets(robot, targets), reached_distance);
+    }
+    static std::vector<fks::Configuration> FlatTargets(const DerivedRobotType& robot, const std::vector<Configuration, ConfigAlloc>& targets) {
+        std::vector<fks::Configuration> flat;
+        for (const auto& t : targets) flat.push_back(robot.ToFlat(t));
+        return flat;
+    }
     static std::vector<std::vector<fks::Configuration>> FlatGroups(const DerivedRobotType& robot,
                                                                    const std::vector<std::vector<Configuration, ConfigAlloc>>& groups) {
         std::vector<std::vector<fks::Configuration>> flat(groups.size());

@@ -140,6 +140,74 @@ struct FlatClusterGroups {
   private:
     uint32_t spare_ = 0;
 };
+/* What SummarizeClusters returns (fks_summarize_clusters in fks_capi.h): every array has N rows, N the
+ * groups' configurations together; row group_begin[g] + c is cluster c of group g (its child state:
+ * members [begin, begin + count) of `members`, their expectation and variances), the rows of empty
+ * clusters are zero.  `reached` is empty when no targets were given. */
+struct ClusterSummaries {
+    size_t width = 0, var_width = 0; /* doubles per row of members / expectation, and of variances */
+    std::vector<uint64_t> group_begin;
+    std::vector<uint32_t> order, count, begin, reached;
+    std::vector<double> members, expectation, variances, variance;
+};
+/* groups, labels and targets laid end to end for fks_summarize_clusters, with the result's arrays */
+struct FlatSummaryGroups {
+    std::vector<double> configs, targets;
+    std::vector<uint32_t> labels;
+    ClusterSummaries out;
+    fks_cluster_summary summary;
+    FlatSummaryGroups(const std::vector<std::vector<Configuration>>& groups, const std::vector<std::vector<uint32_t>>& group_labels,
+                      const std::vector<Configuration>& group_targets, size_t W, size_t Wv) {
+        if (group_labels.size() != groups.size()) throw std::invalid_argument("one label array per group");
+        if (!group_targets.empty() && group_targets.size() != groups.size()) throw std::invalid_argument("one target per group, or none");
+        out.width = W;
+        out.var_width = Wv;
+        out.group_begin.assign(groups.size() + 1, 0);
+        for (size_t g = 0; g < groups.size(); ++g) {
+            if (group_labels[g].size() != groups[g].size()) throw std::invalid_argument("one label per configuration");
+            for (const Configuration& c : groups[g]) {
+                if (c.size() != W) throw std::invalid_argument("configuration has the wrong width");
+                configs.insert(configs.end(), c.begin(), c.end());
+            }
+            labels.insert(labels.end(), group_labels[g].begin(), group_labels[g].end());
+            out.group_begin[g + 1] = out.group_begin[g] + groups[g].size();
+        }
+        for (const Configuration& t : group_targets) {
+            if (t.size() != W) throw std::invalid_argument("target has the wrong width");
+            targets.insert(targets.end(), t.begin(), t.end());
+        }
+        const size_t N = (size_t)out.group_begin.back();
+        out.order.resize(N);
+        out.count.resize(N);
+        out.begin.resize(N);
+        if (!group_targets.empty()) out.reached.resize(N);
+        out.members.resize(N * W);
+        out.expectation.resize(N * W);
+        out.variances.resize(N * Wv);
+        out.variance.resize(N);
+        /* (a spare word for empty vectors: fks_summarize_clusters takes NULL as "not asked for") */
+        summary.order = out.order.empty() ? &spare_u_ : out.order.data();
+        summary.count = out.count.empty() ? &spare_u_ : out.count.data();
+        summary.begin = out.begin.empty() ? &spare_u_ : out.begin.data();
+        summary.reached = group_targets.empty() ? nullptr : (out.reached.empty() ? &spare_u_ : out.reached.data());
+        summary.members = out.members.empty() ? &spare_d_ : out.members.data();
+        summary.expectation = out.expectation.empty() ? &spare_d_ : out.expectation.data();
+        summary.variances = out.variances.empty() ? &spare_d_ : out.variances.data();
+        summary.variance = out.variance.empty() ? &spare_d_ : out.variance.data();
+    }
+    FlatSummaryGroups(const FlatSummaryGroups&) = delete; /* summary points into this object */
+    FlatSummaryGroups& operator=(const FlatSummaryGroups&) = delete;
+    const double* targets_or_null() const { return summary.reached ? (targets.empty() ? &spare_d_ : targets.data()) : nullptr; }
+    uint64_t num_groups() const { return out.group_begin.size() - 1; }
+
+  private:
+    uint32_t spare_u_ = 0;
+    double spare_d_ = 0.0;
+};
+/* W (linked), 3 (SE(2)), 6 (SE(3)): the doubles of a row of variances */
+inline size_t SummaryVarianceWidth(const fks_robot_desc& d, size_t W) {
+    return d.robot_type == FKS_ROBOT_LINKED ? W : (d.robot_type == FKS_ROBOT_SE2 ? 3 : 6);
+}
 /* What ForwardSimulateRobotsUnderPolicy returns: results[leg][particle] as a path's (a leg a
  * particle did not run holds the configuration it stopped at and no contact; target_config is
  * the chosen entry's action, or the configuration itself for such a leg), choices and distances
@@ -615,6 +683,33 @@ class HipParticleContactSimulator {
                                                   flat.matrices_or_null(), flat.labels_ptr(), flat.counts_ptr());
         if (st != FKS_OK) throw SimulatorError(st, std::string("ClusterOutcomesHost: ") + fks_status_string(st));
         return flat.result(want_distances);
+    }
+    /* The planner's step after the clustering (fks_summarize_clusters_ctx): every cluster of every
+     * group made into a child state (its regrouped members, their expectation, per-dimension and
+     * scalar variances and, with one target per group, the members within reached_distance of it),
+     * in one launch.  labels[g] is what ClusterOutcomes returned for groups[g].  Byte for byte what
+     * SummarizeClustersHost returns; no call index is consumed and no statistics move. */
+    ClusterSummaries SummarizeClusters(const RobotDescription& immutable_robot, const std::vector<std::vector<Configuration>>& groups,
+                                       const std::vector<std::vector<uint32_t>>& labels, const std::vector<Configuration>& targets = {},
+                                       double reached_distance = 0.0) {
+        SetRobot(immutable_robot);
+        const size_t W = (size_t)immutable_robot.ConfigurationWidth();
+        FlatSummaryGroups flat(groups, labels, targets, W, SummaryVarianceWidth(immutable_robot.View(), W));
+        dev_.summarize_clusters(flat.configs.data(), flat.out.group_begin.data(), flat.num_groups(), flat.labels.data(),
+                                flat.targets_or_null(), reached_distance, &flat.summary, "SummarizeClusters");
+        return std::move(flat.out);
+    }
+    /* fks_summarize_clusters: the same on the host, with the kernels' arithmetic and without a simulator */
+    static ClusterSummaries SummarizeClustersHost(const RobotDescription& robot, const std::vector<std::vector<Configuration>>& groups,
+                                                  const std::vector<std::vector<uint32_t>>& labels,
+                                                  const std::vector<Configuration>& targets = {}, double reached_distance = 0.0) {
+        const size_t W = (size_t)robot.ConfigurationWidth();
+        const fks_robot_desc d = robot.View();
+        FlatSummaryGroups flat(groups, labels, targets, W, SummaryVarianceWidth(d, W));
+        const fks_status st = fks_summarize_clusters(&d, flat.configs.data(), flat.out.group_begin.data(), flat.num_groups(),
+                                                     flat.labels.data(), flat.targets_or_null(), reached_distance, &flat.summary);
+        if (st != FKS_OK) throw SimulatorError(st, std::string("SummarizeClustersHost: ") + fks_status_string(st));
+        return std::move(flat.out);
     }
     /* Many independent calls in one launch (fks_forward_simulate_jobs; no reference counterpart:
      * the planner's stream of small ForwardSimulateRobots / ReverseSimulateRobots calls, whose

@@ -606,6 +606,103 @@ fks_status fks_cluster_configs_device(fks_context* ctx, const double* d_configs,
 fks_status fks_cluster_configs_ctx(fks_context* ctx, const double* configs, const uint64_t* group_begin, uint64_t num_groups,
                                    double threshold, double* out_distances, uint32_t* out_labels, uint32_t* out_num_clusters);
 
+/* Cluster summaries (added within ABI 10): the planner's step after the clustering, every cluster
+ * of every group made into a child state.  configs [N][W], group_begin [G + 1] (a host array) and
+ * labels [N] are as a clustering call leaves them; targets [G][W], one per group, is optional and
+ * goes with reached_distance.  The configurations are taken as the bytes given: no ResetPosition.
+ *
+ * Clusters and rows.  Cluster c of group g (n configurations) is {i : labels[i] == c} for c in
+ * [0, n), whatever produced the labels: no density or ordering of the labels is assumed, and a
+ * configuration whose label is >= n belongs to no cluster (none of the entries refuses it or
+ * touches a row outside the group because of it).  Cluster c of group g owns row
+ * r = group_begin[g] + c of every per-cluster output, so every such array has N rows, no prefix
+ * over cluster counts exists and no count has to be downloaded to size a buffer.  Rows below
+ * group_begin[0] belong to no group and are left as they are.
+ *
+ * Outputs (fks_cluster_summary: each pointer may be NULL, not all of them).
+ *   order [N]         the stable regrouping: within group g, positions group_begin[g] ... hold the
+ *                     indices into configs of cluster 0's members in ascending index, then cluster
+ *                     1's, and so on; the configurations of no cluster come last, ascending.
+ *   members [N][W]    members[k] = configs[order[k]], a byte copy: a cluster's members are
+ *                     contiguous rows, fit to be the starts of a next fks_job.
+ *   count [N]         the members of the row's cluster.
+ *   begin [N]         the position in order / members of the cluster's first member; for an empty
+ *                     cluster the position its first member would have (group_begin[g] + the
+ *                     members of the group's clusters below c).
+ *   expectation [N][W]
+ *                     a limited dof (revolute, prismatic) and the SE(2) x, y: sum / count.  A
+ *                     continuous dof and the SE(2) angle: atan2(sum of sin, sum of cos) in the
+ *                     portable libm (fks_portable_math.h).  SE(3): entries 3, 7, 11 are sum / count;
+ *                     the rotation block is that of the unit quaternion e which is the eigenvector
+ *                     of the largest eigenvalue of S = sum of q q^T (Markley's mean; it does not
+ *                     depend on the signs of the q), as stated below.
+ *   variances [N][Wv] Wv = W (linked), 3 (SE(2)), 6 (SE(3)): sum of d^2 / count (the population
+ *                     form), d the raw difference from the expectation to the member: c_i[k] - E[k],
+ *                     through wrap_revolute for a continuous dof and the SE(2) angle; for SE(3) the
+ *                     six components of log_twist34(compose34(inverse34(E), c_i)).
+ *   variance [N]      sum of config_distance(cfg = E, target = c_i)^2 / count.
+ *   reached [N]       only with targets: the members with config_distance(cfg = c_i, target =
+ *                     targets[g]) < reached_distance, strict (SPCS:899); a NaN distance never counts.
+ * Every sum over a cluster's members adds the terms (products and squares rounded first, no fused
+ * multiply-add) one by one in ascending member index, starting from +0.0; host and device use this
+ * one order, so the device entries equal the twin byte for byte.  The row of an empty cluster is
+ * count 0, begin as stated, every double +0.0, reached 0.
+ *
+ * The rotation mean.  q = (w, x, y, z) of a member's rotation block R by Shepperd's rule: the
+ * largest of (R00 + R11 + R22, R00, R11, R22), the lowest index winning a tie, names the component
+ * c = sqrt(1 +- ...) / 2 taken from the diagonal; the other three are the matching sums or
+ * differences of off-diagonal entries times 0.25 / c.  q is not normalised.  S's ten entries are
+ * sums of the products q_a q_b.  Cyclic Jacobi on A = S, V = I: sweeps over (p, q) in the order
+ * (0,1)(0,2)(0,3)(1,2)(1,3)(2,3), at most 16 sweeps.  At a pair: an A[p][q] that is zero is
+ * passed; one with |A[p][q]| <= 2^-80 (A00 + A11 + A22 + A33), the trace taken before the first
+ * sweep, is set to zero and passed; otherwise theta = (A[q][q] - A[p][p]) / (2 A[p][q]),
+ * t = sign(theta) / (|theta| + sqrt(theta^2 + 1)) (sign(0) = +1), c = 1 / sqrt(t^2 + 1), s = t c;
+ * A[p][p] -= t A[p][q], A[q][q] += t A[p][q], A[p][q] = 0, and for the other rows r
+ * (A[r][p], A[r][q]) <- (c A[r][p] - s A[r][q], s A[r][p] + c A[r][q]), mirrored; V's columns p
+ * and q alike for every row.  The iteration stops after a sweep that rotated nothing, or at the
+ * cap.  The eigenvector is V's column of the largest A[k][k], the lowest k winning a tie, divided
+ * by its norm; the rotation block is 1 - 2 (yy + zz), 2 (xy - wz), ... of its components, every
+ * entry a product of two of them.  Only + - * / and sqrt are used (csrc/fks_rotation_mean.h is the
+ * one definition, shared by host and device).
+ *
+ * Parity with the planner's own averaging and variance code (uncertainty_planning_core,
+ * arc_utilities) is not pinned: the entries are held to this statement and to nothing else.
+ *
+ * Limits and refusals.  A group holds at most FKS_MAX_CLUSTER_GROUP configurations, N is at most
+ * 2^31, G is below 2^31.  Refused with FKS_ERR_INVALID_ARGUMENT before anything is staged: a NULL
+ * summary or every output NULL, NULL group_begin with G > 0, non-ascending offsets, N above 2^31,
+ * a group above the bound, NULL labels or configs with N > 0, reached without targets or targets
+ * without reached, a NaN reached_distance when targets are given, a malformed robot (host twin);
+ * FKS_ERR_NO_ROBOT for a context without a robot.  The device entries word every refusal in
+ * fks_get_last_error.  Empty groups and G == 0 succeed. */
+typedef struct fks_cluster_summary {
+    uint32_t* order;     /* [N] */
+    double* members;     /* [N][W] */
+    uint32_t* count;     /* [N] */
+    uint32_t* begin;     /* [N] */
+    double* expectation; /* [N][W] */
+    double* variances;   /* [N][Wv] */
+    double* variance;    /* [N] */
+    uint32_t* reached;   /* [N], with targets only */
+} fks_cluster_summary;
+/* The host twin: no context, no GPU.  The device entries below equal it byte for byte. */
+fks_status fks_summarize_clusters(const fks_robot_desc* robot, const double* configs, const uint64_t* group_begin,
+                                  uint64_t num_groups, const uint32_t* labels, const double* targets, double reached_distance,
+                                  const fks_cluster_summary* out);
+/* The same in one launch for the context's robot.  group_begin is a host array, staged by the
+ * entry; d_configs, d_labels, d_targets and every pointer of d_out are in HBM (the summary struct
+ * itself is a host struct).  Stream and synchronize as fks_forward_simulate_device.  The call
+ * consumes no call index and touches no statistics, work counters or last-call counters.  The
+ * per-member terms of the sums lie in a workspace the context owns, grown on demand and freed
+ * with the context. */
+fks_status fks_summarize_clusters_device(fks_context* ctx, const double* d_configs, const uint64_t* group_begin, uint64_t num_groups,
+                                         const uint32_t* d_labels, const double* d_targets, double reached_distance,
+                                         const fks_cluster_summary* d_out, void* stream, int32_t synchronize);
+/* The same on host buffers: one upload, one download per output array. */
+fks_status fks_summarize_clusters_ctx(fks_context* ctx, const double* configs, const uint64_t* group_begin, uint64_t num_groups,
+                                      const uint32_t* labels, const double* targets, double reached_distance,
+                                      const fks_cluster_summary* out);
+
 /* CheckConfigCollision (SPCS:1398-1416) for a batch of n configurations (host
  * buffers): SetPosition(config), CheckEnvironmentCollision at threshold
  * inflation_ratio * res (SPCS:1403, 921-981) and CheckSelfCollisions at extended
