@@ -12,12 +12,12 @@ import subprocess
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
-SOURCES = ["csrc/fks_kernels.hip", "csrc/fks_capi.cpp", "csrc/fks_batch.cpp", "csrc/fks_robot.cpp", "csrc/fks_multi.cpp",
+SOURCES = ["csrc/fks_kernels.hip", "csrc/fks_capi.cpp", "csrc/fks_batch.cpp", "csrc/fks_robot.cpp", "csrc/fks_launch.cpp", "csrc/fks_multi.cpp",
            "csrc/fks_env_builder.cpp",
            "csrc/fks_env_gpu.hip", "csrc/fks_robot_control.cpp", "csrc/fks_policy_select.cpp", "csrc/fks_cluster.cpp",
            "csrc/fks_summary.cpp", "csrc/fks_specialize.cpp"]
 HEADERS = ["csrc/fks_batch.h", "csrc/fks_buffers.h", "csrc/fks_device.h", "csrc/fks_env_internal.h", "csrc/fks_host_distance.h",
-           "csrc/fks_robot.h", "csrc/fks_rotation_mean.h", "csrc/fks_se3.h", "csrc/fks_specialize.h",
+           "csrc/fks_kernel_list.h", "csrc/fks_launch.h", "csrc/fks_robot.h", "csrc/fks_rotation_mean.h", "csrc/fks_se3.h", "csrc/fks_specialize.h",
            "../include/fks_capi.h", "../include/fks_portable_math.h", "../include/fks_control.h"]
 # the kernel source and the headers it includes, carried inside the library for the run-time
 # compilation of shape-specialised kernels (fks_specialize.cpp): name as included -> path
@@ -253,6 +253,13 @@ def build_robot_flatten_test(force: bool = False) -> str:
     """tests/cpp/robot_flatten_test.cpp with csrc/fks_robot.cpp, the host-only checks, dof numbering, tables and
     skip-proof constants of a robot description, and the SDF analysis."""
     return _build_host_test("robot_flatten_test", ("csrc/fks_robot.cpp",), ROBOT_HEADERS, force)
+
+
+def build_launch_plan_test(force: bool = False) -> str:
+    """tests/cpp/launch_plan_test.cpp with csrc/fks_launch.cpp, the host-only launch decisions: a robot's layout
+    against a fake occupancy query, the kernel and module build of a call, the grid, and the kernel list."""
+    return _build_host_test("launch_plan_test", ("csrc/fks_launch.cpp",), PLAN_HEADERS + ("csrc/fks_launch.h", "csrc/fks_kernel_list.h"),
+                            force)
 
 
 def build_buffers_test(force: bool = False) -> str:

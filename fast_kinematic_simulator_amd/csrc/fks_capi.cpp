@@ -25,113 +25,63 @@
 #include "fks_batch.h"
 #include "fks_buffers.h"
 #include "fks_env_internal.h"
+#include "fks_launch.h"
 #include "fks_robot.h"
 #include "fks_specialize.h"
 #include "fks_device.h"
 #include "fks_portable_math.h"
 
-extern "C" __global__ void fks_simulate_linked(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_indiv(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_indiv(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_indiv(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_traced(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_traced(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_traced(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_coop(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_coop(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_coop(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_lean(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_lean_indiv(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_lean_traced(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_path(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_lean_path(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_path(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_path(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_path_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_path_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_path_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_jobs(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_lean_jobs(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_jobs(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_jobs(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_jobs_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_jobs_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_jobs_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_path_jobs(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_lean_path_jobs(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_path_jobs(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_path_jobs(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_path_jobs_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se2_path_jobs_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_se3_path_jobs_small(const fksd::SimArgs* args);
-extern "C" __global__ void fks_simulate_linked_policy(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
-extern "C" __global__ void fks_simulate_linked_lean_policy(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
-extern "C" __global__ void fks_simulate_se2_policy(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
-extern "C" __global__ void fks_simulate_se3_policy(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
-extern "C" __global__ void fks_simulate_linked_policy_small(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
-extern "C" __global__ void fks_simulate_se2_policy_small(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
-extern "C" __global__ void fks_simulate_se3_policy_small(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
+/* the kernels that take a SimArgs: fks_kernel_list.h's rows */
+#define FKS_KERNEL(symbol, ...) extern "C" __global__ void symbol(const fksd::SimArgs* args);
+#define FKS_POLICY_KERNEL(symbol, ...) extern "C" __global__ void symbol(const fksd::SimArgs* args, const fksd::PolicyArgs* pol);
+#include "fks_kernel_list.h"
 extern "C" __global__ void fks_cluster_linked(const fksd::ClusterArgs args);
 extern "C" __global__ void fks_cluster_se2(const fksd::ClusterArgs args);
 extern "C" __global__ void fks_cluster_se3(const fksd::ClusterArgs args);
 extern "C" __global__ void fks_summary_linked(const fksd::SummaryArgs args);
 extern "C" __global__ void fks_summary_se2(const fksd::SummaryArgs args);
 extern "C" __global__ void fks_summary_se3(const fksd::SummaryArgs args);
-extern "C" __global__ void fks_check_configs_linked(const fksd::SimArgs* args);
-extern "C" __global__ void fks_check_configs_se2(const fksd::SimArgs* args);
-extern "C" __global__ void fks_check_configs_se3(const fksd::SimArgs* args);
-extern "C" __global__ void fks_kinematics_linked(const fksd::SimArgs* args);
-extern "C" __global__ void fks_kinematics_se2(const fksd::SimArgs* args);
-extern "C" __global__ void fks_kinematics_se3(const fksd::SimArgs* args);
 extern "C" __global__ void fks_math_probe(const double* a, const double* b, double* out, uint64_t n);
 
 namespace {
 
-typedef void (*sim_kernel_t)(const fksd::SimArgs*);
+using fks_launch::family_of;
+using fks_launch::KernelId;
 
-/* The library's kernels by form, register budget and robot family (FKS.cpp:4-71 factories).
- * Forms: the plain simulation, its individual-Jacobian, traced and cooperative (one particle per
- * workgroup) instantiations, the batched CheckConfigCollision, and the three batched forms in the
- * order of fks_batch::Form.  Budget: throughput, or the low-occupancy instantiation for batches
- * that fit its resident waves.  Family: a linked robot's lean LDS block (fks_set_robot) has
- * kernels of its own where the throughput budget has them, the linked one's otherwise. */
-enum KernelForm { KF_PLAIN = 0, KF_INDIVIDUAL, KF_TRACED, KF_COOP, KF_CHECK, KF_PATH, KF_JOBS, KF_PATH_JOBS, KF_COUNT };
-static_assert(KF_JOBS == KF_PATH + fks_batch::JOBS && KF_PATH_JOBS == KF_PATH + fks_batch::PATH_JOBS, "batched forms in Form order");
-const sim_kernel_t kKernels[KF_COUNT][2][4] = {
-    /* linked, linked lean, SE(2), SE(3) */
-    {{fks_simulate_linked, fks_simulate_linked_lean, fks_simulate_se2, fks_simulate_se3},
-     {fks_simulate_linked_small, fks_simulate_linked_small, fks_simulate_se2_small, fks_simulate_se3_small}},
-    {{fks_simulate_linked_indiv, fks_simulate_linked_lean_indiv, fks_simulate_se2_indiv, fks_simulate_se3_indiv}, {}},
-    {{fks_simulate_linked_traced, fks_simulate_linked_lean_traced, fks_simulate_se2_traced, fks_simulate_se3_traced}, {}},
-    {{fks_simulate_linked_coop, fks_simulate_linked_coop, fks_simulate_se2_coop, fks_simulate_se3_coop}, {}},
-    {{fks_check_configs_linked, fks_check_configs_linked, fks_check_configs_se2, fks_check_configs_se3}, {}},
-    {{fks_simulate_linked_path, fks_simulate_linked_lean_path, fks_simulate_se2_path, fks_simulate_se3_path},
-     {fks_simulate_linked_path_small, fks_simulate_linked_path_small, fks_simulate_se2_path_small, fks_simulate_se3_path_small}},
-    {{fks_simulate_linked_jobs, fks_simulate_linked_lean_jobs, fks_simulate_se2_jobs, fks_simulate_se3_jobs},
-     {fks_simulate_linked_jobs_small, fks_simulate_linked_jobs_small, fks_simulate_se2_jobs_small, fks_simulate_se3_jobs_small}},
-    {{fks_simulate_linked_path_jobs, fks_simulate_linked_lean_path_jobs, fks_simulate_se2_path_jobs, fks_simulate_se3_path_jobs},
-     {fks_simulate_linked_path_jobs_small, fks_simulate_linked_path_jobs_small, fks_simulate_se2_path_jobs_small,
-      fks_simulate_se3_path_jobs_small}},
-};
-sim_kernel_t kernel_of(int form, bool small, int robot_type, bool lean = false) {
-    const int family = robot_type == FKS_ROBOT_SE2 ? 2 : (robot_type == FKS_ROBOT_SE3 ? 3 : (lean ? 1 : 0));
-    return kKernels[form][small ? 1 : 0][family];
-}
-/* the policy roll-out's kernels (fks_forward_simulate_policy): the path kernels' POLICY flavour,
- * with the call's PolicyArgs as their second argument; by budget and family as above */
+/* the list's kernels by row, each signature in an array of its own (a policy roll-out's kernels
+ * take the call's PolicyArgs second); the function of an identity (fks_launch::kernel_row), null
+ * where the library has none of that signature */
+typedef void (*sim_kernel_t)(const fksd::SimArgs*);
 typedef void (*policy_kernel_t)(const fksd::SimArgs*, const fksd::PolicyArgs*);
-const policy_kernel_t kPolicyKernels[2][4] = {
-    {fks_simulate_linked_policy, fks_simulate_linked_lean_policy, fks_simulate_se2_policy, fks_simulate_se3_policy},
-    {fks_simulate_linked_policy_small, fks_simulate_linked_policy_small, fks_simulate_se2_policy_small, fks_simulate_se3_policy_small}};
-policy_kernel_t policy_kernel_of(bool small, int robot_type, bool lean) {
-    const int family = robot_type == FKS_ROBOT_SE2 ? 2 : (robot_type == FKS_ROBOT_SE3 ? 3 : (lean ? 1 : 0));
-    return kPolicyKernels[small ? 1 : 0][family];
+const sim_kernel_t kSimKernels[] = {
+#define FKS_KERNEL(symbol, ...) symbol,
+#define FKS_POLICY_KERNEL(symbol, ...) nullptr,
+#include "fks_kernel_list.h"
+};
+const policy_kernel_t kPolicyKernels[] = {
+#define FKS_KERNEL(symbol, ...) nullptr,
+#define FKS_POLICY_KERNEL(symbol, ...) symbol,
+#include "fks_kernel_list.h"
+};
+static_assert(sizeof(kSimKernels) / sizeof(kSimKernels[0]) == fks_launch::kKernelRows, "one function per row");
+sim_kernel_t sim_kernel_of(const KernelId& id) {
+    const int row = fks_launch::kernel_row(id);
+    return row < 0 ? nullptr : kSimKernels[row];
 }
+policy_kernel_t policy_kernel_of(const KernelId& id) {
+    const int row = fks_launch::kernel_row(id);
+    return row < 0 ? nullptr : kPolicyKernels[row];
+}
+/* ... as the runtime's attribute and occupancy queries take it */
+const void* kernel_of(const KernelId& id) {
+    const sim_kernel_t k = sim_kernel_of(id);
+    return k ? reinterpret_cast<const void*>(k) : reinterpret_cast<const void*>(policy_kernel_of(id));
+}
+/* the clustering and summary kernels by family (they have no lean form) */
+void (*const kClusterKernels[fks_launch::FAMILY_COUNT])(const fksd::ClusterArgs) = {fks_cluster_linked, fks_cluster_linked, fks_cluster_se2,
+                                                                                   fks_cluster_se3};
+void (*const kSummaryKernels[fks_launch::FAMILY_COUNT])(const fksd::SummaryArgs) = {fks_summary_linked, fks_summary_linked, fks_summary_se2,
+                                                                                   fks_summary_se3};
 
 using fks_batch::splitmix64;
 using fks_buf::DeviceBuffer;
@@ -284,16 +234,7 @@ struct fks_context {
     RobotBuffers robot;
     /* launch resources */
     DeviceBuffer<double> d_scratch; /* the persistent grid's per-wave workspaces */
-    uint64_t scratch_per_wave = 0;
-    uint32_t grid_waves = 0;
-    uint32_t waves_per_cu = 0;     /* resident waves per CU of the layout (LDS and registers) */
-    uint32_t small_grid_waves = 0; /* resident waves of the small-batch kernel (0: none for this layout) */
-    uint32_t coop_particles = 0;   /* resident workgroups (particles) of the cooperative kernel (0: none) */
-    uint32_t coop_waves = 0;       /* its waves per workgroup */
-    size_t coop_lds_bytes = 0;
-    uint32_t grid_groups = 0;
-    uint32_t waves_per_group = fksd::kWavesPerGroup;
-    size_t lds_bytes = 0;
+    fks_launch::Layout lay;         /* the current robot's layout (fks_set_robot) */
     MirroredBuffer<unsigned long long> counters; /* kNumCounters + queue + phase cycles, and their pinned copy */
     uint64_t phase_last[FKS_NUM_PHASES] = {};
     uint64_t phase_total[FKS_NUM_PHASES] = {};
@@ -337,9 +278,6 @@ struct fks_context {
     int32_t individual_jacobians = 0; /* fks_set_individual_jacobians (SPCS:420-423) */
     int32_t small_batch = 1;          /* fks_set_small_batch_kernel */
     int32_t cooperative = 0;          /* fks_set_cooperative_waves (opt-in: DESIGN.md §5.4) */
-    bool fk_pair = false;             /* paired FK of free microsteps (fks_set_robot) */
-    bool lean = false;                /* lean LDS block + lean kernels (fks_set_robot) */
-    uint32_t standard_resident_waves = 0; /* resident waves of the non-lean layout (fks_get_launch_info) */
     int32_t last_kernel = FKS_KERNEL_NONE;       /* the simulation kernel of the last call */
     int32_t last_check_kernel = FKS_KERNEL_NONE; /* the configuration-check kernel of the last check */
     DeviceBuffer<double> d_seg_state;
@@ -401,13 +339,13 @@ static fks_spec::Shape spec_shape_of(const fks_context* ctx) {
     sh.W = ctx->R.W;
     sh.G = ctx->R.G;
     sh.P = ctx->R.P;
-    sh.pair = ctx->fk_pair ? 1 : 0;
-    sh.lean = ctx->lean ? 1 : 0;
+    sh.pair = ctx->lay.fk_pair ? 1 : 0;
+    sh.lean = ctx->lay.lean ? 1 : 0;
     sh.no_proofs = ctx->specialize == FKS_SPECIALIZE_NO_PROOFS ? 1 : 0;
     /* the waves a SIMD holds at this layout (4 SIMDs per CU): when the LDS block keeps fewer
      * resident than the register budget allows (cfg5's lean blocks: 16 per CU), the
      * specialised kernel is compiled for that many and may use their registers */
-    const int per_simd = (int)((ctx->waves_per_cu + 3) / 4);
+    const int per_simd = (int)((ctx->lay.waves_per_cu + 3) / 4);
     if (per_simd >= 1 && per_simd < fksd::kThroughputWavesPerEU) sh.waves_per_eu = per_simd;
     /* FKS_SPEC_WAVES_PER_EU=n (tuning and A/B runs): compile for n waves per SIMD instead
      * (n >= the layout's waves; 0 = the library's budget) */
@@ -443,13 +381,12 @@ static fks_status spec_load(fks_context* ctx, const fks_spec::Shape& sh, std::sh
     return FKS_OK;
 }
 
-/* the throughput register budget of a shaped kernel: the persistent grid is sized for the
- * generic kernel's occupancy, so a specialised kernel (same launch bounds, same LDS block) is
- * used only if it needs no more registers.  512 VGPRs per SIMD lane, allocated in granules of 8 */
+/* the throughput register budget of a shaped kernel, against the generic kernel it replaces */
 static int spec_budget(const fks_context* ctx, const fks_spec::Shape& sh) {
     hipFuncAttributes gen{};
-    if (hipFuncGetAttributes(&gen, reinterpret_cast<const void*>(kernel_of(KF_PLAIN, false, ctx->R.type, ctx->lean))) != hipSuccess) gen.numRegs = 0;
-    return sh.waves_per_eu > 0 ? (512 / sh.waves_per_eu) & ~7 : gen.numRegs;
+    const KernelId generic{fks_launch::PLAIN, fks_launch::THROUGHPUT, family_of(ctx->R.type, ctx->lay.lean)};
+    if (hipFuncGetAttributes(&gen, kernel_of(generic)) != hipSuccess) gen.numRegs = 0;
+    return fks_launch::throughput_register_budget(sh.waves_per_eu, gen.numRegs);
 }
 
 /* VGPRs plus AGPRs of kernel `name`, read from the code object's metadata (the runtime's
@@ -495,9 +432,9 @@ static fks_status shaped_build(fks_context* ctx, ShapedModule* sm, const ShapedK
     /* ... and the small-batch kernel, used when it needs no more registers than two waves per
      * SIMD leave (the generic small-batch kernel's grid is the one launched) */
     hipFunction_t fs = nullptr;
-    if (!ctx->lean && hipModuleGetFunction(&fs, m, kind.small_fn) == hipSuccess) {
+    if (!ctx->lay.lean && hipModuleGetFunction(&fs, m, kind.small_fn) == hipSuccess) {
         const int v = spec_registers(*co, kind.small_fn);
-        if (v > 0 && v <= 256) sm->small_fn = fs;
+        if (v > 0 && v <= fks_launch::kSmallRegisterBound) sm->small_fn = fs;
     }
     (void)hipGetLastError();
     sm->seconds = compiled ? co->compile_seconds : 0.0;
@@ -532,12 +469,40 @@ static void shaped_build_pending(fks_context* ctx, ShapedModule* sm, const Shape
     (void)hipSetDevice(ctx->device);
 }
 
-/* whether a path, job or path-job batch runs the shaped batch kernels; builds the module at
- * the first batch that would run its throughput kernel (a small batch never builds it) */
-static bool bspec_ready(fks_context* ctx, bool small) {
-    if (!ctx->bspec_enabled || ctx->specialize != FKS_SPECIALIZE_ON || ctx->individual_jacobians) return false;
-    if (ctx->bspec.pending && !small) shaped_build_pending(ctx, &ctx->bspec, kBatchedModule);
-    return small ? (ctx->bspec.fn && ctx->bspec.small_fn && !ctx->lean) : ctx->bspec.fn != nullptr;
+/* what the kernel decision (fks_launch.h) reads of the context and of a module */
+static fks_launch::Settings launch_settings(const fks_context* ctx) {
+    fks_launch::Settings s;
+    s.robot_type = ctx->R.type;
+    s.small_batch = ctx->small_batch != 0;
+    s.cooperative = ctx->cooperative != 0;
+    s.individual_jacobians = ctx->individual_jacobians != 0;
+    s.specialize = ctx->specialize;
+    s.bspec_enabled = ctx->bspec_enabled != 0;
+    s.lean = ctx->lay.lean;
+    s.coop_particles = ctx->lay.coop_particles;
+    s.grid_waves = ctx->lay.grid_waves;
+    return s;
+}
+static fks_launch::ModuleState module_state(const ShapedModule& m) {
+    return fks_launch::ModuleState{m.fn != nullptr, m.small_fn != nullptr, m.check_fn != nullptr, m.pending};
+}
+
+/* The kernel of a request: the pending module the decision names is built first, then the decision
+ * is taken on what there is.  *module and *function: the shaped one that runs, or null */
+static fks_launch::Choice decide_kernel(fks_context* ctx, const fks_launch::Request& rq, ShapedModule** module, hipFunction_t* function) {
+    const fks_launch::Settings s = launch_settings(ctx);
+    switch (fks_launch::module_to_build(s, module_state(ctx->spec), module_state(ctx->bspec), rq)) {
+        case fks_launch::MODULE_PLAIN: shaped_build_pending(ctx, &ctx->spec, kPlainModule); break;
+        case fks_launch::MODULE_BATCHED: shaped_build_pending(ctx, &ctx->bspec, kBatchedModule); break;
+        case fks_launch::MODULE_NONE: break;
+    }
+    const fks_launch::Choice c = fks_launch::choose_kernel(s, module_state(ctx->spec), module_state(ctx->bspec), rq);
+    ShapedModule* m = c.module == fks_launch::MODULE_PLAIN ? &ctx->spec : (c.module == fks_launch::MODULE_BATCHED ? &ctx->bspec : nullptr);
+    *module = m;
+    *function = !m ? nullptr
+                   : (c.function == fks_launch::FUNCTION_SMALL ? m->small_fn
+                                                               : (c.function == fks_launch::FUNCTION_CHECK ? m->check_fn : m->fn));
+    return c;
 }
 
 extern "C" {
@@ -709,130 +674,34 @@ const char* fks_get_last_error(const fks_context* ctx) { return ctx ? ctx->last_
 
 int32_t fks_config_width(const fks_context* ctx) { return (ctx && ctx->has_robot) ? ctx->R.W : 0; }
 
-/* Launch geometry of the current robot: the LDS layout (with the paired FK's second set
- * of joint motion matrices for linked chains of <= 32 joints when the occupancy it leaves
- * equals the plain layout's), workgroup size, resident workgroups per CU and the per-wave
- * workspace.  Computed into locals and committed to ctx only when all of it succeeds. */
+/* the occupancy calls behind fks_launch::plan_layout's questions: a failure answers 0 */
+struct RuntimeQueries final : fks_launch::Queries {
+    int resident_blocks(const KernelId& id, uint32_t threads, size_t lds_bytes) const override {
+        int n = 0;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel_of(id), (int)threads, lds_bytes) == hipSuccess ? n : 0;
+    }
+    int max_threads(const KernelId& id) const override {
+        hipFuncAttributes fa{};
+        return hipFuncGetAttributes(&fa, kernel_of(id)) == hipSuccess ? fa.maxThreadsPerBlock : 0;
+    }
+};
+
+/* Launch geometry of the current robot: fks_launch::plan_layout on what the device answers, and
+ * the workspace it asks for.  Committed to ctx only when all of it succeeds. */
 static fks_status launch_layout(fks_context* ctx, const fksd::RobotDev& R) {
-    const int P = R.P, G = R.G;
-    /* resident waves per CU of a layout at the largest workgroup (<= wmax waves) whose
-     * blocks fit the CU's 160 KiB */
-    auto blocks = [&](const fksd::LdsLayout& l, uint32_t wmax, uint32_t* wpg, size_t* bytes) -> int {
-        uint32_t w = wmax;
-        size_t b = 0;
-        for (;;) {
-            b = ((size_t)l.shared_total + (size_t)w * l.total) * sizeof(double);
-            if (b <= 160 * 1024 || w == 1) break;
-            w /= 2;
-        }
-        *wpg = w;
-        *bytes = b;
-        if (b > 160 * 1024) return 0;
-        /* every kernel launched with this layout (plain, individual-Jacobian and traced
-         * simulation, configuration check, kinematics) must hold that many groups: the
-         * smallest occupancy of them all */
-        const bool lean_l = l.lean != 0;
-        const sim_kernel_t kernels[] = {kernel_of(KF_PLAIN, false, R.type, lean_l), kernel_of(KF_INDIVIDUAL, false, R.type, lean_l),
-                                        kernel_of(KF_TRACED, false, R.type, lean_l), kernel_of(KF_CHECK, false, R.type),
-                                        R.type == FKS_ROBOT_SE2 ? fks_kinematics_se2
-                                                                : (R.type == FKS_ROBOT_SE3 ? fks_kinematics_se3 : fks_kinematics_linked)};
-        int n = 1 << 30;
-        for (sim_kernel_t k : kernels) {
-            int nk = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nk, reinterpret_cast<const void*>(k), 64 * (int)w, b) != hipSuccess)
-                return 0;
-            n = std::min(n, nk);
-        }
-        return n * (int)w; /* resident waves per CU */
-    };
-    uint32_t wpg = 0;
-    size_t bytes = 0;
-    const bool linked_pairable = R.type == FKS_ROBOT_LINKED && R.J >= 1 && R.J <= 32;
-    const int w0 = blocks(fksd::make_lds_layout(R.L, R.J, R.D, R.W, R.G, R.nrounds), fksd::kWavesPerGroup, &wpg, &bytes);
-    bool pair = false;
-    if (linked_pairable && w0 > 0) {
-        uint32_t w = 0;
-        size_t b = 0;
-        pair = blocks(fksd::make_lds_layout(R.L, R.J, R.D, R.W, R.G, R.nrounds, true), fksd::kWavesPerGroup, &w, &b) >= w0;
-    }
-    int waves_per_cu = blocks(fksd::make_lds_layout(R.L, R.J, R.D, R.W, R.G, R.nrounds, pair), fksd::kWavesPerGroup, &wpg, &bytes);
-    const int standard_waves_per_cu = waves_per_cu;
-    /* a linked robot whose LDS block caps the resident waves below the register limit may run
-     * lean blocks (the skip-proof cache in scratch) in workgroups of up to 8 waves, if that
-     * keeps more waves resident (cfg5's 14-dof arm: 12 -> 16 per CU) */
-    bool lean = false;
-    if (R.type == FKS_ROBOT_LINKED) {
-        for (uint32_t wmax : {(uint32_t)fksd::kMaxWavesPerGroup, (uint32_t)fksd::kWavesPerGroup}) {
-            uint32_t w = 0;
-            size_t b = 0;
-            const int n = blocks(fksd::make_lds_layout(R.L, R.J, R.D, R.W, R.G, R.nrounds, false, true), wmax, &w, &b);
-            if (n > waves_per_cu) {
-                waves_per_cu = n;
-                wpg = w;
-                bytes = b;
-                lean = true;
-                pair = false;
-            }
-        }
-    }
-    if (waves_per_cu < 1)
-        return fail(ctx, FKS_ERR_UNSUPPORTED,
-                    "robot too large: one wave's LDS block (" + std::to_string(bytes) + " bytes) does not fit a CU");
-    int cus = 0;
-    HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    uint32_t grid_groups = (uint32_t)(cus * (waves_per_cu / (int)wpg));
-    const uint64_t scratch_per_wave = fksd::make_scratch_layout(3u * P, R.D, (int)P, G).total;
-    /* the per-wave workspace grows with 3P x D (the stacked Jacobian) and the robot's
-     * geometry count: for very large robots the persistent grid keeps only as many waves
-     * as half the free HBM holds (the ticket queue hands out the work either way) */
+    fks_launch::LayoutInputs in{};
+    in.robot = fks_launch::RobotShape{R.type, R.L, R.J, R.D, R.W, R.G, R.P, R.nrounds};
+    HIP_TRY(ctx, hipDeviceGetAttribute(&in.cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     size_t free_b = 0, total_b = 0;
     HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-    free_b += ctx->d_scratch.capacity() * sizeof(double); /* the current workspace is given back below */
-    const size_t per_group = (size_t)wpg * scratch_per_wave * sizeof(double);
-    const size_t max_groups = std::max<size_t>(1, (free_b / 2) / std::max<size_t>(1, per_group));
-    if ((size_t)grid_groups > max_groups) grid_groups = (uint32_t)max_groups;
-    const size_t words = (size_t)grid_groups * wpg * scratch_per_wave;
-    HIP_TRY(ctx, ctx->d_scratch.reserve(words)); /* frees the current workspace before it allocates a larger one */
-    ctx->fk_pair = pair;
-    ctx->lean = lean;
-    ctx->standard_resident_waves = (uint32_t)(cus * std::max(0, standard_waves_per_cu));
-    ctx->waves_per_cu = (uint32_t)waves_per_cu;
-    ctx->waves_per_group = wpg;
-    ctx->lds_bytes = bytes;
-    ctx->grid_groups = grid_groups;
-    ctx->grid_waves = grid_groups * wpg;
-    /* the small-batch kernel on the same layout (not for lean blocks) */
-    ctx->small_grid_waves = 0;
-    if (!lean) {
-        int nk = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nk, reinterpret_cast<const void*>(kernel_of(KF_PLAIN, true, R.type)), 64 * (int)wpg,
-                                                         bytes) == hipSuccess &&
-            nk > 0)
-            ctx->small_grid_waves = std::min<uint32_t>((uint32_t)(cus * nk) * wpg, ctx->grid_waves);
-    }
-    /* the cooperative kernel: one wave's block plus the mailbox per workgroup, its workgroup
-     * size from its launch bound (a build's FKS_COOP_WAVES); each workgroup uses one wave's
-     * workspace, so at most grid_waves of them */
-    ctx->coop_particles = 0;
-    ctx->coop_waves = 0;
-    ctx->coop_lds_bytes = 0;
-    if (!lean && R.nrounds <= fksd::kCoopMaxRounds) {
-        const fksd::LdsLayout l = fksd::make_lds_layout(R.L, R.J, R.D, R.W, R.G, R.nrounds, pair);
-        const size_t cb = ((size_t)l.shared_total + l.total + fksd::kCoopBoxDoubles) * sizeof(double);
-        hipFuncAttributes fa{};
-        int nk = 0;
-        if (cb <= 160 * 1024 && hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel_of(KF_COOP, false, R.type))) == hipSuccess &&
-            fa.maxThreadsPerBlock >= 128 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nk, reinterpret_cast<const void*>(kernel_of(KF_COOP, false, R.type)),
-                                                         fa.maxThreadsPerBlock, cb) == hipSuccess &&
-            nk > 0) {
-            ctx->coop_waves = (uint32_t)fa.maxThreadsPerBlock / 64u;
-            ctx->coop_lds_bytes = cb;
-            ctx->coop_particles = std::min<uint32_t>((uint32_t)(cus * nk), ctx->grid_waves);
-        }
-    }
-    (void)hipGetLastError();
-    ctx->scratch_per_wave = scratch_per_wave;
+    in.free_hbm_bytes = free_b + ctx->d_scratch.capacity() * sizeof(double); /* the current workspace is given back below */
+    fks_launch::Layout lay;
+    std::string why;
+    const fks_status st = fks_launch::plan_layout(in, RuntimeQueries(), &lay, &why);
+    if (st != FKS_OK) return fail(ctx, st, why);
+    HIP_TRY(ctx, ctx->d_scratch.reserve((size_t)lay.scratch_words)); /* frees the current workspace before it allocates a larger one */
+    (void)hipGetLastError(); /* an occupancy query that failed leaves the runtime's error set */
+    ctx->lay = lay;
     return FKS_OK;
 }
 
@@ -993,6 +862,33 @@ struct TraceDev {
     uint32_t step_cap, cfg_cap;
 };
 
+/* the arguments every kernel that takes a SimArgs reads: the grids, the robot, the solver
+ * parameters and the layout with its workspace; for the simulation and the configuration check
+ * also the environment and the counters (the kinematics leaves them zero); everything else zero */
+static fksd::SimArgs base_args(const fks_context* ctx, bool environment) {
+    fksd::SimArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.sdf_g = ctx->sdf_g;
+    a.nrm_g = ctx->nrm_g;
+    a.env_g = ctx->env_g;
+    a.R = ctx->R;
+    a.S = ctx->params;
+    a.scratch = ctx->d_scratch.get();
+    a.scratch_per_wave = ctx->lay.scratch_per_wave;
+    a.row_cap = 3u * (uint32_t)ctx->R.P;
+    a.L = fksd::make_lds_layout(ctx->R.L, ctx->R.J, ctx->R.D, ctx->R.W, ctx->R.G, ctx->R.nrounds, ctx->lay.fk_pair, ctx->lay.lean);
+    a.SL = fksd::make_scratch_layout(a.row_cap, ctx->R.D, ctx->R.P, ctx->R.G);
+    if (!environment) return a;
+    a.sdf = ctx->d_sdf.get();
+    a.nrange = ctx->d_nrange.get();
+    a.nent = ctx->d_nent.get();
+    a.oob = ctx->oob;
+    a.has_normals = ctx->has_normals;
+    a.counters = ctx->counters.dev();
+    a.queue = ctx->counters.dev() + fksd::kNumCounters;
+    return a;
+}
+
 /* what the plan of a launch (fks_batch.h) reads of the context: its schedule settings and the
  * arguments every call on it shares */
 static void plan_inputs(const fks_context* ctx, fks_batch::Inputs* in) {
@@ -1000,31 +896,21 @@ static void plan_inputs(const fks_context* ctx, fks_batch::Inputs* in) {
     in->call_index = ctx->call_index;
     in->T = forward_steps(ctx->params.forward_simulation_time, std::fabs(ctx->frequency));
     in->segment_steps = ctx->segment_steps;
-    in->grid_waves = ctx->grid_waves;
-    in->small_grid_waves = ctx->small_grid_waves;
+    in->grid_waves = ctx->lay.grid_waves;
+    in->small_grid_waves = ctx->lay.small_grid_waves;
     in->small_batch = ctx->small_batch != 0;
     in->individual_jacobians = ctx->individual_jacobians != 0;
-    in->lean = ctx->lean;
+    in->lean = ctx->lay.lean;
     in->W = (uint32_t)ctx->R.W;
     in->seg_stride = 2u * (uint32_t)ctx->R.D + 4u + (uint32_t)fksd::kRoundState * (uint32_t)std::min(ctx->R.nrounds, 64);
     in->heavy_per_step = ctx->heavy_per_step;
     in->heavy_priority = ctx->heavy_priority;
     in->heavy_relative = ctx->heavy_relative;
     fksd::SimArgs& a = in->base;
-    std::memset(&a, 0, sizeof(a));
-    a.sdf_g = ctx->sdf_g;
-    a.nrm_g = ctx->nrm_g;
-    a.env_g = ctx->env_g;
-    a.sdf = ctx->d_sdf.get();
-    a.nrange = ctx->d_nrange.get();
-    a.nent = ctx->d_nent.get();
-    a.oob = ctx->oob;
-    a.has_normals = ctx->has_normals;
+    a = base_args(ctx, true);
     a.skip_enabled = ctx->skip_enabled;
     a.skip_lplus = ctx->skip_lplus;
     a.skip_cmax = ctx->skip_cmax;
-    a.R = ctx->R;
-    a.S = ctx->params;
     a.dt = 1.0 / ctx->frequency;
     a.thr_env = 0.0 - (ctx->params.environment_collision_check_tolerance * ctx->sdf_g.res);
     a.target_micro = ctx->env_g.res * 0.125;
@@ -1032,13 +918,6 @@ static void plan_inputs(const fks_context* ctx, fks_batch::Inputs* in) {
     a.time_multiplier = 1.0 / a.dt;
     a.T = in->T;
     a.individual_jacobians = ctx->individual_jacobians;
-    a.counters = ctx->counters.dev();
-    a.queue = ctx->counters.dev() + fksd::kNumCounters;
-    a.scratch = ctx->d_scratch.get();
-    a.scratch_per_wave = ctx->scratch_per_wave;
-    a.row_cap = 3u * (uint32_t)ctx->R.P;
-    a.L = fksd::make_lds_layout(ctx->R.L, ctx->R.J, ctx->R.D, ctx->R.W, ctx->R.G, ctx->R.nrounds, ctx->fk_pair, ctx->lean);
-    a.SL = fksd::make_scratch_layout(a.row_cap, ctx->R.D, ctx->R.P, ctx->R.G);
     a.seg_stride = in->seg_stride;
 }
 
@@ -1072,73 +951,41 @@ static fks_job plain_call(const double* d_starts, uint64_t n, const double* d_ta
     return c;
 }
 
-/* what a request launches: one of the library's kernels, or one of a shaped module's */
-struct Launch {
-    int32_t kind = FKS_KERNEL_NONE; /* fks_get_launch_info: last_kernel */
-    sim_kernel_t kernel = nullptr;
-    policy_kernel_t policy = nullptr; /* a policy roll-out's kernel: launched with the call's PolicyArgs */
+/* From the zeroed counters to the queued copy of them: decides the kernel of `what` (decide_kernel),
+ * launches it over `args` between the two events (a policy roll-out's kernel with `pol`) and leaves
+ * the call pending or settled.  *kind: last_kernel, or last_check_kernel of a check */
+static fks_status launch_request(fks_context* ctx, const fks_launch::Request& what, const fksd::SimArgs* args,
+                                 const fksd::PolicyArgs* pol, hipStream_t s, int32_t synchronize, int32_t* kind) {
+    const bool check = what.kind == fks_launch::REQUEST_CHECK;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.dev(), 0, fksd::kCounterWords * sizeof(unsigned long long), s));
+    ShapedModule* module = nullptr;
     hipFunction_t shaped = nullptr;
-    ShapedModule* module = nullptr; /* of `shaped`: its launches are counted */
-    bool coop = false;              /* the cooperative geometry: one workgroup per particle */
-};
-
-/* The kernel of a request over n particles under `plan`.  A pending shaped module is built
- * here, at the first launch that would run its throughput kernel (never for a small batch:
- * robots only ever simulated in small batches cost no compile). */
-static Launch choose_kernel(fks_context* ctx, const SimRequest& rq, const fks_batch::SegmentPlan& plan, uint64_t n) {
-    Launch l;
-    const int rt = ctx->R.type;
-    if (rq.batch) {
-        /* the robot's batched module serves all three forms through its PATH && JOBS kernel when
-         * the records fit its bound; otherwise the generic kernel of the batch's own form */
-        const fks_batch::Batch& b = *rq.batch;
-        if (b.policy) {
-            /* always the generic policy kernels, also when a batched shaped module exists */
-            l.kind = plan.small ? FKS_KERNEL_POLICY_SMALL_BATCH : FKS_KERNEL_POLICY;
-            l.policy = policy_kernel_of(plan.small, rt, ctx->lean);
-            return l;
-        }
-        static const int32_t kGeneric[3][2] = {{FKS_KERNEL_PATH, FKS_KERNEL_PATH_SMALL_BATCH},
-                                               {FKS_KERNEL_JOBS, FKS_KERNEL_JOBS_SMALL_BATCH},
-                                               {FKS_KERNEL_PATH_JOBS, FKS_KERNEL_PATH_JOBS_SMALL_BATCH}};
-        if (b.legs <= FKS_MAX_PATH_JOB_LEGS && bspec_ready(ctx, plan.small)) {
-            l.kind = plan.small ? FKS_KERNEL_SHAPED_PATH_JOBS_SMALL_BATCH : FKS_KERNEL_SHAPED_PATH_JOBS;
-            l.shaped = plan.small ? ctx->bspec.small_fn : ctx->bspec.fn;
-            l.module = &ctx->bspec;
-        } else {
-            l.kind = kGeneric[b.form][plan.small ? 1 : 0];
-            l.kernel = kernel_of(KF_PATH + b.form, plan.small, rt, ctx->lean);
-        }
-        return l;
-    }
-    const bool individual = ctx->individual_jacobians != 0;
-    if (rq.trace) {
-        l.kind = FKS_KERNEL_TRACED;
-        l.kernel = kernel_of(KF_TRACED, false, rt, ctx->lean);
-    } else if (ctx->small_batch && ctx->cooperative && !individual && !ctx->lean && plan.nseg == 1 && n > 0 &&
-               n <= (uint64_t)ctx->coop_particles) {
-        l.kind = FKS_KERNEL_COOPERATIVE;
-        l.kernel = kernel_of(KF_COOP, false, rt);
-        l.coop = true;
-    } else if (plan.small) {
-        /* the shape's small-batch kernel once the robot's module is built */
-        const bool shaped = ctx->spec.fn && ctx->spec.small_fn;
-        l.kind = shaped ? FKS_KERNEL_SHAPED_SMALL_BATCH : FKS_KERNEL_SMALL_BATCH;
-        l.shaped = shaped ? ctx->spec.small_fn : nullptr;
-        l.module = shaped ? &ctx->spec : nullptr;
-        l.kernel = kernel_of(KF_PLAIN, true, rt);
-    } else if (individual) {
-        l.kind = FKS_KERNEL_INDIVIDUAL;
-        l.kernel = kernel_of(KF_INDIVIDUAL, false, rt, ctx->lean);
+    const fks_launch::Choice l = decide_kernel(ctx, what, &module, &shaped);
+    const fks_launch::Geometry g = fks_launch::launch_geometry(ctx->lay, what.n, l.cooperative);
+    /* the list has a kernel of this identity, of the signature that is launched */
+    const sim_kernel_t kernel = sim_kernel_of(l.generic);
+    const policy_kernel_t policy = policy_kernel_of(l.generic);
+    if (!shaped && !(pol ? policy != nullptr : kernel != nullptr)) return fail(ctx, FKS_ERR_UNSUPPORTED, "no kernel for this request");
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
+    if (!check) *kind = l.kind; /* a simulation reports its kernel also when the launch fails, a check only once it is issued */
+    if (shaped) {
+        void* params[] = {&args};
+        HIP_TRY(ctx, hipModuleLaunchKernel(shaped, g.blocks, 1, 1, g.threads, 1, 1, (unsigned)g.lds_bytes, s, params, nullptr));
+        if (!check) module->launches++;
+    } else if (pol) {
+        hipLaunchKernelGGL(policy, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, args, pol);
     } else {
-        /* the plain throughput path runs the robot's shape-specialised kernel */
-        if (ctx->spec.pending) shaped_build_pending(ctx, &ctx->spec, kPlainModule);
-        l.kind = ctx->spec.fn ? FKS_KERNEL_SHAPED : FKS_KERNEL_THROUGHPUT;
-        l.shaped = ctx->spec.fn;
-        l.module = ctx->spec.fn ? &ctx->spec : nullptr;
-        l.kernel = kernel_of(KF_PLAIN, false, rt, ctx->lean);
+        hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds_bytes, s, args);
     }
-    return l;
+    if (check) *kind = l.kind;
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->counters.host(), ctx->counters.dev(), fksd::kCounterWords * sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, s));
+    ctx->pending = true;
+    ctx->pending_kind = check ? 1 : 0;
+    ctx->pending_stream = s;
+    return synchronize ? settle(ctx) : FKS_OK;
 }
 
 static fks_status simulate_device(fks_context* ctx, const SimRequest& rq) {
@@ -1222,36 +1069,15 @@ static fks_status simulate_device(fks_context* ctx, const SimRequest& rq) {
         }
         HIP_TRY(ctx, hipMemcpyAsync(ctx->args.dev(), ctx->args.host(), sizeof(a), hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.dev(), 0, fksd::kCounterWords * sizeof(unsigned long long), s));
-    const uint64_t groups_needed = (n + ctx->waves_per_group - 1) / ctx->waves_per_group;
-    const uint32_t grid = (uint32_t)((groups_needed < (uint64_t)ctx->grid_groups) ? (groups_needed > 0 ? groups_needed : 1)
-                                                                                  : ctx->grid_groups);
-    const Launch l = choose_kernel(ctx, rq, plan, n);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    ctx->last_kernel = l.kind;
-    if (l.shaped) {
-        const fksd::SimArgs* argp = d_launch_args;
-        void* params[] = {&argp};
-        HIP_TRY(ctx, hipModuleLaunchKernel(l.shaped, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes, s, params,
-                                           nullptr));
-        l.module->launches++;
-    } else if (l.policy) {
-        const fksd::PolicyArgs* pol = reinterpret_cast<const fksd::PolicyArgs*>(ctx->path_args.dev() + records.policy_record);
-        hipLaunchKernelGGL(l.policy, dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args, pol);
-    } else if (l.coop) {
-        hipLaunchKernelGGL(l.kernel, dim3((uint32_t)n), dim3(64 * ctx->coop_waves), ctx->coop_lds_bytes, s, d_launch_args);
-    } else {
-        hipLaunchKernelGGL(l.kernel, dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s, d_launch_args);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->counters.host(), ctx->counters.dev(), fksd::kCounterWords * sizeof(unsigned long long),
-                                hipMemcpyDeviceToHost, s));
-    ctx->pending = true;
-    ctx->pending_kind = 0;
-    ctx->pending_stream = s;
-    if (rq.synchronize) return settle(ctx);
-    return FKS_OK;
+    fks_launch::Request what;
+    what.kind = tr ? fks_launch::REQUEST_TRACED : fks_launch::REQUEST_PLAIN;
+    if (batch) what = fks_launch::Request{fks_launch::REQUEST_BATCH, batch->form, batch->policy, batch->legs};
+    what.n = n;
+    what.small = plan.small;
+    what.nseg = plan.nseg;
+    const fksd::PolicyArgs* pol =
+        batch && batch->policy ? reinterpret_cast<const fksd::PolicyArgs*>(ctx->path_args.dev() + records.policy_record) : nullptr;
+    return launch_request(ctx, what, d_launch_args, pol, s, rq.synchronize, &ctx->last_kernel);
 }
 
 extern "C" {
@@ -1284,18 +1110,7 @@ fks_status fks_check_config_collision_device(fks_context* ctx, const double* d_c
     std::memset(&ctx->check_last, 0, sizeof(ctx->check_last));
     ctx->check_last.particles = n;
     if (n == 0) return FKS_OK;
-    fksd::SimArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.sdf_g = ctx->sdf_g;
-    a.nrm_g = ctx->nrm_g;
-    a.env_g = ctx->env_g;
-    a.sdf = ctx->d_sdf.get();
-    a.nrange = ctx->d_nrange.get();
-    a.nent = ctx->d_nent.get();
-    a.oob = ctx->oob;
-    a.has_normals = ctx->has_normals;
-    a.R = ctx->R;
-    a.S = ctx->params;
+    fksd::SimArgs a = base_args(ctx, true);
     /* SPCS:1403-1404 thresholds, SPCS:923 tolerance */
     a.thr_env = (inflation_ratio * ctx->env_g.res) - (ctx->params.environment_collision_check_tolerance * ctx->sdf_g.res);
     a.self_res = (inflation_ratio + 1.0) * ctx->env_g.res;
@@ -1303,42 +1118,15 @@ fks_status fks_check_config_collision_device(fks_context* ctx, const double* d_c
     a.n = n;
     a.out_collided = d_out_collided;
     a.out_err = d_out_error_flags;
-    a.counters = ctx->counters.dev();
-    a.queue = ctx->counters.dev() + fksd::kNumCounters;
-    a.scratch = ctx->d_scratch.get();
-    a.scratch_per_wave = ctx->scratch_per_wave;
-    a.row_cap = 3u * (uint32_t)ctx->R.P;
-    a.L = fksd::make_lds_layout(ctx->R.L, ctx->R.J, ctx->R.D, ctx->R.W, ctx->R.G, ctx->R.nrounds, ctx->fk_pair, ctx->lean);
-    a.SL = fksd::make_scratch_layout(a.row_cap, ctx->R.D, ctx->R.P, ctx->R.G);
     *ctx->args.host() = a;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->args.dev(), ctx->args.host(), sizeof(a), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.dev(), 0, fksd::kCounterWords * sizeof(unsigned long long), s));
-    const uint64_t groups_needed = (n + ctx->waves_per_group - 1) / ctx->waves_per_group;
-    const uint32_t grid = (uint32_t)((groups_needed < (uint64_t)ctx->grid_groups) ? groups_needed : ctx->grid_groups);
-    /* a batch larger than the resident grid runs the robot's shape-specialised check (built
-     * here if the simulation has not built the module yet; a failure keeps the generic one) */
-    if (ctx->spec.pending && n > (uint64_t)ctx->grid_waves) shaped_build_pending(ctx, &ctx->spec, kPlainModule);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    if (ctx->spec.check_fn) {
-        const fksd::SimArgs* argp = ctx->args.dev();
-        void* params[] = {&argp};
-        HIP_TRY(ctx, hipModuleLaunchKernel(ctx->spec.check_fn, grid, 1, 1, 64 * ctx->waves_per_group, 1, 1, (unsigned)ctx->lds_bytes,
-                                           s, params, nullptr));
-        ctx->last_check_kernel = FKS_KERNEL_SHAPED;
-    } else {
-        hipLaunchKernelGGL(kernel_of(KF_CHECK, false, ctx->R.type), dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, s,
-                           static_cast<const fksd::SimArgs*>(ctx->args.dev()));
-        ctx->last_check_kernel = FKS_KERNEL_THROUGHPUT;
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->counters.host(), ctx->counters.dev(), fksd::kCounterWords * sizeof(unsigned long long),
-                                hipMemcpyDeviceToHost, s));
-    ctx->pending = true;
-    ctx->pending_kind = 1;
-    ctx->pending_stream = s;
-    if (synchronize) return settle(ctx);
-    return FKS_OK;
+    /* a batch larger than the resident grid builds the robot's module if the simulation has not
+     * built it yet (a failure keeps the generic check); the module's shape-specialised check runs
+     * whenever the module is there, whatever the batch's size */
+    fks_launch::Request what;
+    what.kind = fks_launch::REQUEST_CHECK;
+    what.n = n;
+    return launch_request(ctx, what, ctx->args.dev(), nullptr, s, synchronize, &ctx->last_check_kernel);
 }
 
 fks_status fks_check_config_collision(fks_context* ctx, const double* configs, uint64_t n, double inflation_ratio,
@@ -1677,9 +1465,7 @@ static fks_status cluster_device(fks_context* ctx, const fks_batch::ClusterPlan&
     a.out_num_clusters = d_out_num_clusters;
     a.work = plan.work_words ? ctx->d_cluster_work.get() : nullptr;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(plan.num_groups, 1u << 16);
-    void (*kernel)(const fksd::ClusterArgs) =
-        ctx->R.type == FKS_ROBOT_LINKED ? fks_cluster_linked : (ctx->R.type == FKS_ROBOT_SE2 ? fks_cluster_se2 : fks_cluster_se3);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(fksd::kClusterThreads), 0, s, a);
+    hipLaunchKernelGGL(kClusterKernels[family_of(ctx->R.type, false)], dim3(grid), dim3(fksd::kClusterThreads), 0, s, a);
     HIP_TRY(ctx, hipGetLastError());
     ctx->pending = true;
     ctx->pending_kind = 2;
@@ -1774,9 +1560,7 @@ static fks_status summary_device(fks_context* ctx, const fks_batch::SummaryPlan&
     a.out_variance = d_out.variance;
     a.out_reached = d_out.reached;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(plan.num_groups, 1u << 16);
-    void (*kernel)(const fksd::SummaryArgs) =
-        ctx->R.type == FKS_ROBOT_LINKED ? fks_summary_linked : (ctx->R.type == FKS_ROBOT_SE2 ? fks_summary_se2 : fks_summary_se3);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(fksd::kSummaryThreads), 0, s, a);
+    hipLaunchKernelGGL(kSummaryKernels[family_of(ctx->R.type, false)], dim3(grid), dim3(fksd::kSummaryThreads), 0, s, a);
     HIP_TRY(ctx, hipGetLastError());
     ctx->pending = true;
     ctx->pending_kind = 2;
@@ -2017,31 +1801,20 @@ fks_status fks_kinematics(fks_context* ctx, int32_t mode, const double* configs,
     if (e == hipSuccess && mode == FKS_KIN_APPLY_CONTROL_INPUT) e = upload(d_in, inputs, (size_t)n * D);
     if (e == hipSuccess) e = d_out.reserve((size_t)n * per_out);
     if (e != hipSuccess) return hip_fail(ctx, e, "kinematics buffers");
-    fksd::SimArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.sdf_g = ctx->sdf_g;
-    a.nrm_g = ctx->nrm_g;
-    a.env_g = ctx->env_g;
-    a.R = ctx->R;
-    a.S = ctx->params;
+    fksd::SimArgs a = base_args(ctx, false);
     a.starts = d_cfg.get();
     a.targets = d_in.get();
     a.n = n;
-    a.scratch = ctx->d_scratch.get();
-    a.scratch_per_wave = ctx->scratch_per_wave;
-    a.row_cap = 3u * (uint32_t)ctx->R.P;
-    a.L = fksd::make_lds_layout(ctx->R.L, ctx->R.J, ctx->R.D, ctx->R.W, ctx->R.G, ctx->R.nrounds, ctx->fk_pair, ctx->lean);
-    a.SL = fksd::make_scratch_layout(a.row_cap, ctx->R.D, ctx->R.P, ctx->R.G);
     a.kin_mode = mode;
     a.kin_out = d_out.get();
     *ctx->args.host() = a;
     e = hipMemcpy(ctx->args.dev(), ctx->args.host(), sizeof(a), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        const uint64_t groups_needed = (n + ctx->waves_per_group - 1) / ctx->waves_per_group;
-        const uint32_t grid = (uint32_t)((groups_needed < (uint64_t)ctx->grid_groups) ? groups_needed : ctx->grid_groups);
-        sim_kernel_t k = (ctx->R.type == FKS_ROBOT_SE2) ? fks_kinematics_se2
-                                                        : (ctx->R.type == FKS_ROBOT_SE3 ? fks_kinematics_se3 : fks_kinematics_linked);
-        hipLaunchKernelGGL(k, dim3(grid), dim3(64 * ctx->waves_per_group), ctx->lds_bytes, nullptr,
+        const fks_launch::Geometry g = fks_launch::launch_geometry(ctx->lay, n);
+        const KernelId id{fks_launch::KINEMATICS, fks_launch::THROUGHPUT, family_of(ctx->R.type, ctx->lay.lean)};
+        const sim_kernel_t k = sim_kernel_of(id);
+        if (!k) return fail(ctx, FKS_ERR_UNSUPPORTED, "no kinematics kernel for this robot");
+        hipLaunchKernelGGL(k, dim3(g.blocks), dim3(g.threads), g.lds_bytes, nullptr,
                            static_cast<const fksd::SimArgs*>(ctx->args.dev()));
         e = hipGetLastError();
     }
@@ -2231,8 +2004,8 @@ fks_status fks_get_specialization(const fks_context* ctx, fks_specialization_inf
 fks_status fks_get_launch_geometry(const fks_context* ctx, uint32_t* resident_waves, uint64_t* lds_bytes_per_group) {
     if (!ctx || !resident_waves || !lds_bytes_per_group) return FKS_ERR_INVALID_ARGUMENT;
     if (!ctx->has_robot) return FKS_ERR_NO_ROBOT;
-    *resident_waves = ctx->grid_waves;
-    *lds_bytes_per_group = (uint64_t)ctx->lds_bytes;
+    *resident_waves = ctx->lay.grid_waves;
+    *lds_bytes_per_group = (uint64_t)ctx->lay.lds_bytes;
     return FKS_OK;
 }
 
@@ -2240,17 +2013,17 @@ fks_status fks_get_launch_info(const fks_context* ctx, fks_launch_info* out) {
     if (!ctx || !out) return FKS_ERR_INVALID_ARGUMENT;
     if (!ctx->has_robot) return FKS_ERR_NO_ROBOT;
     std::memset(out, 0, sizeof(*out));
-    out->resident_waves = ctx->grid_waves;
-    out->waves_per_group = ctx->waves_per_group;
-    out->lds_bytes_per_group = (uint64_t)ctx->lds_bytes;
-    out->small_batch_resident_waves = ctx->small_grid_waves;
-    out->standard_layout_resident_waves = ctx->standard_resident_waves;
-    out->fk_pair = ctx->fk_pair ? 1 : 0;
-    out->lean = ctx->lean ? 1 : 0;
+    out->resident_waves = ctx->lay.grid_waves;
+    out->waves_per_group = ctx->lay.waves_per_group;
+    out->lds_bytes_per_group = (uint64_t)ctx->lay.lds_bytes;
+    out->small_batch_resident_waves = ctx->lay.small_grid_waves;
+    out->standard_layout_resident_waves = ctx->lay.standard_resident_waves;
+    out->fk_pair = ctx->lay.fk_pair ? 1 : 0;
+    out->lean = ctx->lay.lean ? 1 : 0;
     out->last_kernel = ctx->last_kernel;
     out->last_check_kernel = ctx->last_check_kernel;
-    out->cooperative_resident_particles = ctx->coop_particles;
-    out->cooperative_waves_per_particle = ctx->coop_waves;
+    out->cooperative_resident_particles = ctx->lay.coop_particles;
+    out->cooperative_waves_per_particle = ctx->lay.coop_waves;
     return FKS_OK;
 }
 

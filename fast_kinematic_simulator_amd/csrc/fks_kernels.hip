@@ -4524,259 +4524,34 @@ fks_simulate_shaped_small(const SimArgs* __restrict__ args) {
 }
 #endif
 #elif !defined(FKS_SHAPE_L)
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false>(args, lds_mem);
-}
-
-/* small batches (fks_set_small_batch_kernel): at most two waves per SIMD, so the register
- * budget holds the whole working set without spills.  One particle per wave and no
- * segments, chosen only when the batch fits its resident waves: such a batch is the
- * latency of its slowest particle, not a throughput problem (cfg1: 3.8-3.9 ms against
- * 4.2-4.35, profiles/r04j_occupancy_ab_cfg1.log). */
+/* the library's kernels: the rows of fks_kernel_list.h, defined in its order (a row's flavour
+ * names simulate_particles' template arguments) */
 #define FKS_SMALL_KERNEL_ATTRS __launch_bounds__(64 * kMaxWavesPerGroup) __attribute__((amdgpu_waves_per_eu(2)))
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_linked_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false>(args, lds_mem);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false>(args, lds_mem);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false>(args, lds_mem);
-}
-
-/* cooperative small batches (fks_set_cooperative_waves): one particle per workgroup of
- * FKS_COOP_WAVES waves, whose environment checks and correction passes are shared out over
- * them (COOP above); for batches up to one particle per workgroup slot */
 #define FKS_COOP_KERNEL_ATTRS __launch_bounds__(64 * FKS_COOP_WAVES) __attribute__((amdgpu_waves_per_eu(2)))
-extern "C" __global__ void FKS_COOP_KERNEL_ATTRS fks_simulate_linked_coop(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, false, FKS_COOP_WAVES>(args, lds_mem);
-}
-extern "C" __global__ void FKS_COOP_KERNEL_ATTRS fks_simulate_se2_coop(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, false, false, FKS_COOP_WAVES>(args, lds_mem);
-}
-extern "C" __global__ void FKS_COOP_KERNEL_ATTRS fks_simulate_se3_coop(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, false, false, FKS_COOP_WAVES>(args, lds_mem);
-}
-
-/* simulate_with_individual_jacobians = true (SPCS:420, 1629; fks_set_individual_jacobians) */
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_indiv(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_indiv(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_indiv(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, true>(args, lds_mem);
-}
-
-/* traced instantiations: ForwardSimulateRobot with enable_tracing (fks_forward_simulate_traced) */
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_traced(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_traced(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_traced(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, true>(args, lds_mem);
-}
-
-/* lean LDS blocks (LdsLayout.lean: the round skip-proof cache in the wave's scratch), chosen by
- * fks_set_robot for linked robots whose LDS block limits the resident waves (14-dof cfg5) */
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_indiv(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, true, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_traced(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, true, false, true>(args, lds_mem);
-}
-
-/* waypoint paths (fks_forward_simulate_path): PATH instantiations at the throughput budget ... */
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_path(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_path(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, true, 0, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_path(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_path(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true>(args, lds_mem);
-}
-/* ... and at the small-batch budget, for paths whose batch fits its resident waves: the wave
- * carries its particle through every leg (SimArgs.path_carry) */
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_linked_path_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_path_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_path_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true>(args, lds_mem);
-}
-
-/* job batches (fks_forward_simulate_jobs): JOBS instantiations at the throughput budget ... */
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_jobs(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, false, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_jobs(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, true, 0, false, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_jobs(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, false, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_jobs(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, false, true>(args, lds_mem);
-}
-/* ... and at the small-batch budget, for batches whose jobs together fit its resident waves */
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_linked_jobs_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, false, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_jobs_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, false, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_jobs_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, false, true>(args, lds_mem);
-}
-
-/* path-job batches (fks_forward_simulate_path_jobs): PATH && JOBS instantiations at the throughput
- * budget ... */
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_path_jobs(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_path_jobs(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, true, 0, true, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_path_jobs(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_path_jobs(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true, true>(args, lds_mem);
-}
-/* ... and at the small-batch budget, for batches whose jobs together fit its resident waves: a
- * wave carries its particle through its own job's legs */
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_linked_path_jobs_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_path_jobs_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true, true>(args, lds_mem);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_path_jobs_small(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true, true>(args, lds_mem);
-}
-
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_check_configs_linked(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    check_configs<FKS_ROBOT_LINKED>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_check_configs_se2(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    check_configs<FKS_ROBOT_SE2>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_check_configs_se3(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    check_configs<FKS_ROBOT_SE3>(args, lds_mem);
-}
-
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_kinematics_linked(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    kinematics<FKS_ROBOT_LINKED>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_kinematics_se2(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    kinematics<FKS_ROBOT_SE2>(args, lds_mem);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_kinematics_se3(const SimArgs* __restrict__ args) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    kinematics<FKS_ROBOT_SE3>(args, lds_mem);
-}
-
-/* policy roll-outs (fks_forward_simulate_policy): POLICY instantiations of the path kernels at the
- * throughput budget; the second argument is the call's PolicyArgs ... */
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_policy(const SimArgs* __restrict__ args,
-                                                                        const PolicyArgs* __restrict__ pol) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true, false, true>(args, lds_mem, pol);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_linked_lean_policy(const SimArgs* __restrict__ args,
-                                                                             const PolicyArgs* __restrict__ pol) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, true, 0, true, false, true>(args, lds_mem, pol);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se2_policy(const SimArgs* __restrict__ args,
-                                                                     const PolicyArgs* __restrict__ pol) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true, false, true>(args, lds_mem, pol);
-}
-extern "C" __global__ void FKS_KERNEL_ATTRS fks_simulate_se3_policy(const SimArgs* __restrict__ args,
-                                                                     const PolicyArgs* __restrict__ pol) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true, false, true>(args, lds_mem, pol);
-}
-/* ... and at the small-batch budget, for roll-outs whose batch fits its resident waves: the wave
- * carries its particle through every leg until it stops */
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_linked_policy_small(const SimArgs* __restrict__ args,
-                                                                                    const PolicyArgs* __restrict__ pol) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_LINKED, false, false, false, 0, true, false, true>(args, lds_mem, pol);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se2_policy_small(const SimArgs* __restrict__ args,
-                                                                                 const PolicyArgs* __restrict__ pol) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE2, false, false, false, 0, true, false, true>(args, lds_mem, pol);
-}
-extern "C" __global__ void FKS_SMALL_KERNEL_ATTRS fks_simulate_se3_policy_small(const SimArgs* __restrict__ args,
-                                                                                 const PolicyArgs* __restrict__ pol) {
-    extern __shared__ __attribute__((aligned(16))) double lds_mem[];
-    simulate_particles<FKS_ROBOT_SE3, false, false, false, 0, true, false, true>(args, lds_mem, pol);
-}
+#define FKS_ATTRS_THROUGHPUT FKS_KERNEL_ATTRS
+#define FKS_ATTRS_SMALL FKS_SMALL_KERNEL_ATTRS
+#define FKS_ATTRS_COOPERATIVE FKS_COOP_KERNEL_ATTRS
+#define FKS_TYPE_LINKED FKS_ROBOT_LINKED
+#define FKS_TYPE_LINKED_LEAN FKS_ROBOT_LINKED
+#define FKS_TYPE_SE2 FKS_ROBOT_SE2
+#define FKS_TYPE_SE3 FKS_ROBOT_SE3
+enum : unsigned { F_NONE = 0, F_TRACED = 1, F_INDIVIDUAL = 2, F_LEAN = 4, F_COOP = 8, F_PATH = 16, F_JOBS = 32, F_POLICY = 64 };
+#define FKS_ENTRY_simulate_particles(RT, F)                                                                                  \
+    simulate_particles<RT, ((F)&F_TRACED) != 0, ((F)&F_INDIVIDUAL) != 0, ((F)&F_LEAN) != 0, ((F)&F_COOP) ? FKS_COOP_WAVES : 0, \
+                       ((F)&F_PATH) != 0, ((F)&F_JOBS) != 0, ((F)&F_POLICY) != 0>
+#define FKS_ENTRY_check_configs(RT, F) check_configs<RT>
+#define FKS_ENTRY_kinematics(RT, F) kinematics<RT>
+#define FKS_KERNEL(symbol, attributes, entry, flavour, form, budget, family)                          \
+    extern "C" __global__ void FKS_ATTRS_##attributes symbol(const SimArgs* __restrict__ args) {       \
+        extern __shared__ __attribute__((aligned(16))) double lds_mem[];                              \
+        FKS_ENTRY_##entry(FKS_TYPE_##family, flavour)(args, lds_mem);                                  \
+    }
+#define FKS_POLICY_KERNEL(symbol, attributes, entry, flavour, form, budget, family)                                                 \
+    extern "C" __global__ void FKS_ATTRS_##attributes symbol(const SimArgs* __restrict__ args, const PolicyArgs* __restrict__ pol) { \
+        extern __shared__ __attribute__((aligned(16))) double lds_mem[];                                                            \
+        FKS_ENTRY_##entry(FKS_TYPE_##family, flavour)(args, lds_mem, pol);                                                           \
+    }
+#include "fks_kernel_list.h"
 
 #endif /* FKS_SHAPE_L */
 
