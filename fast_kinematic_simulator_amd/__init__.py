@@ -11,7 +11,8 @@ from .robots import (ControllerConfig, Joint, RobotDescription, SampledActuatorM
                      make_sampled_actuator_model, make_se2_robot, make_se3_robot, se3_pose, transform34)
 from .simulator import (HipParticleContactSimulator, MultiDeviceSimulator, PolicyTable, SimulationResult, SimulatorSolverParameters,
                         get_default_solver_parameters, make_linked_simulator, make_se2_simulator, make_se3_simulator,
-                        cluster_outcomes_host, policy_select, summarize_clusters_host, SUMMARY_OUTPUTS)
+                        cluster_outcomes_host, policy_select, summarize_clusters_host, SUMMARY_OUTPUTS,
+                        select_states_host, select_states_plan, SELECT_OUTPUTS, SELECT_TABLE)
 
 __all__ = [
     "FksError", "lib", "ObstacleConfig", "SimulatorEnvironment", "build_complete_environment", "ControllerConfig", "Joint",
@@ -19,4 +20,5 @@ __all__ = [
     "HipParticleContactSimulator", "MultiDeviceSimulator", "SimulationResult", "SimulatorSolverParameters", "get_default_solver_parameters",
     "make_linked_simulator", "make_se2_simulator", "make_se3_simulator", "PolicyTable", "policy_select",
     "cluster_outcomes_host", "summarize_clusters_host", "SUMMARY_OUTPUTS",
+    "select_states_host", "select_states_plan", "SELECT_OUTPUTS", "SELECT_TABLE",
 ]

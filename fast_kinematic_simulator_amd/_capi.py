@@ -247,6 +247,33 @@ class ClusterSummary(ctypes.Structure):
     ]
 
 
+STATE_NONE = 0xFFFFFFFF
+MAX_STATES = 1 << 30
+
+
+class StateTable(ctypes.Structure):
+    """fks_state_table: the resident states of a selection call (host or device pointers, as the entry takes them)."""
+    _fields_ = [
+        ("keys", c_void_p),
+        ("weights", c_void_p),
+        ("count", c_void_p),
+        ("begin", c_void_p),
+        ("members", c_void_p),
+        ("num_states", c_uint64),
+        ("num_member_rows", c_uint64),
+    ]
+
+
+class StateSelection(ctypes.Structure):
+    """fks_state_selection: the outputs of a selection call; all but choice may be NULL."""
+    _fields_ = [
+        ("choice", c_void_p),
+        ("distance", c_void_p),
+        ("starts", c_void_p),
+        ("source", c_void_p),
+    ]
+
+
 class PolicyTable(ctypes.Structure):
     """fks_policy_table: a policy's states (keys), actions (targets) and flags (host or device pointers, as the entry
     takes them) with the two distances of the verdict."""
@@ -395,6 +422,14 @@ PROTOTYPES = [
                                                 POINTER(ClusterSummary), c_void_p, c_int32]),
     ("fks_summarize_clusters_ctx", c_int32, [c_void_p, POINTER(c_double), POINTER(c_uint64), c_uint64, POINTER(c_uint32),
                                              POINTER(c_double), c_double, POINTER(ClusterSummary)]),
+    ("fks_select_states", c_int32, [POINTER(RobotDesc), POINTER(StateTable), POINTER(c_double), c_uint64, c_uint32, c_uint64,
+                                    POINTER(StateSelection)]),
+    ("fks_select_states_device", c_int32, [c_void_p, POINTER(StateTable), c_void_p, c_uint64, c_uint32, c_uint64,
+                                           POINTER(StateSelection), c_void_p, c_int32]),
+    ("fks_select_states_ctx", c_int32, [c_void_p, POINTER(StateTable), POINTER(c_double), c_uint64, c_uint32, c_uint64,
+                                        POINTER(StateSelection)]),
+    ("fks_select_states_plan", c_int32, [c_uint64, c_uint64, c_int32, POINTER(c_uint64)]),
+    ("fks_select_philox", None, [POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]),
     ("fks_forward_simulate_jobs", c_int32, [c_void_p, POINTER(Job), c_uint64]),
     ("fks_forward_simulate_jobs_device", c_int32, [c_void_p, POINTER(Job), c_uint64, c_void_p, c_int32]),
     ("fks_forward_simulate_path_jobs", c_int32, [c_void_p, POINTER(PathJob), c_uint64]),

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(PKG)
 SOURCES = ["csrc/fks_kernels.hip", "csrc/fks_capi.cpp", "csrc/fks_batch.cpp", "csrc/fks_robot.cpp", "csrc/fks_launch.cpp", "csrc/fks_multi.cpp",
            "csrc/fks_env_builder.cpp",
            "csrc/fks_env_gpu.hip", "csrc/fks_robot_control.cpp", "csrc/fks_policy_select.cpp", "csrc/fks_cluster.cpp",
-           "csrc/fks_summary.cpp", "csrc/fks_specialize.cpp"]
+           "csrc/fks_summary.cpp", "csrc/fks_state_select.cpp", "csrc/fks_specialize.cpp"]
 HEADERS = ["csrc/fks_batch.h", "csrc/fks_buffers.h", "csrc/fks_device.h", "csrc/fks_env_internal.h", "csrc/fks_host_distance.h",
            "csrc/fks_kernel_list.h", "csrc/fks_launch.h", "csrc/fks_robot.h", "csrc/fks_rotation_mean.h", "csrc/fks_se3.h", "csrc/fks_specialize.h",
            "../include/fks_capi.h", "../include/fks_portable_math.h", "../include/fks_control.h"]
@@ -249,6 +249,11 @@ def build_summary_plan_test(force: bool = False) -> str:
                             force)
 
 
+def build_select_plan_test(force: bool = False) -> str:
+    """tests/cpp/select_plan_test.cpp with the host-only plan of a state selection and the host twin."""
+    return _build_host_test("select_plan_test", SELECT_SOURCES + ("csrc/fks_state_select.cpp",), SELECT_HEADERS, force)
+
+
 def build_robot_flatten_test(force: bool = False) -> str:
     """tests/cpp/robot_flatten_test.cpp with csrc/fks_robot.cpp, the host-only checks, dof numbering, tables and
     skip-proof constants of a robot description, and the SDF analysis."""
@@ -296,6 +301,16 @@ def build_summary_test(force: bool = False, workspace: bool = False) -> str:
         return build_cpp_program(os.path.join("tests", "cpp", "summary_interface_test.cpp"), "summary_interface_test_workspace",
                                  force, extra_flags=(f"-I{MOCK_WORKSPACE}",), extra_deps=_headers(MOCK_WORKSPACE))
     return build_cpp_program(os.path.join("tests", "cpp", "summary_interface_test.cpp"), "summary_interface_test", force)
+
+
+def build_select_test(force: bool = False, workspace: bool = False) -> str:
+    """Compile tests/cpp/select_interface_test.cpp: SelectStates of the plain class and of the
+    planner drop-in against the C-ABI entries on a table read from a file.  workspace=True puts the
+    mock planner workspace on the include path, as build_planner_test."""
+    if workspace:
+        return build_cpp_program(os.path.join("tests", "cpp", "select_interface_test.cpp"), "select_interface_test_workspace",
+                                 force, extra_flags=(f"-I{MOCK_WORKSPACE}",), extra_deps=_headers(MOCK_WORKSPACE))
+    return build_cpp_program(os.path.join("tests", "cpp", "select_interface_test.cpp"), "select_interface_test", force)
 
 
 def build_shaped_batches_test(force: bool = False) -> str:

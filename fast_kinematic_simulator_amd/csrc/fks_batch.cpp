@@ -422,4 +422,48 @@ fks_status plan_summary(SummaryPlan* p, int32_t robot_type, uint32_t width, cons
     return FKS_OK;
 }
 
+fks_status plan_select(SelectPlan* p, uint32_t width, int32_t compute_units, const fks_state_table* table, const double* queries,
+                       uint64_t num_queries, uint32_t num_particles, const fks_state_selection* out, std::string* why) {
+    *p = SelectPlan();
+    auto refuse = [&](const char* text) {
+        *why = text;
+        return FKS_ERR_INVALID_ARGUMENT;
+    };
+    if (!table) return refuse("null state table");
+    if (!out) return refuse("null selection");
+    if (!table->keys) return refuse("null keys");
+    if (table->num_states == 0) return refuse("a state table holds at least one state");
+    if (table->num_states > FKS_MAX_STATES) return refuse("at most FKS_MAX_STATES (2^30) states");
+    if (num_queries > 0 && !out->choice) return refuse("null choice");
+    if (num_queries > 0 && !queries) return refuse("null queries");
+    const bool draw = out->starts || out->source;
+    if (draw && num_particles == 0) return refuse("starts or source is asked for with num_particles == 0");
+    if (draw && (!table->count || !table->begin || !table->members))
+        return refuse("starts or source is asked for without count, begin and members");
+    if (table->begin && !table->count) return refuse("begin is given without count");
+    if (num_queries > kMaxSelectQueries) return refuse("at most 2^20 queries per call");
+    if (num_particles > kMaxSelectParticles) return refuse("at most 65536 particles per job");
+    if (num_queries * (uint64_t)num_particles > kMaxSelectStarts) return refuse("at most 2^31 starts (queries x particles) per call");
+    p->num_queries = num_queries;
+    p->num_states = table->num_states;
+    p->width = width;
+    p->particles = num_particles;
+    p->draw = draw;
+    p->launch = num_queries > 0;
+    if (!p->launch) return FKS_OK;
+    const uint64_t S = table->num_states, T = fksd::kSelectTile, B = fksd::kSelectThreads;
+    p->tile = (uint32_t)std::min<uint64_t>(T, num_queries);
+    p->tiles = (num_queries + T - 1) / T;
+    const uint64_t cus = (uint64_t)std::max<int32_t>(compute_units, 1);
+    const uint64_t wanted = (kSelectGroupsPerCu * cus + p->tiles - 1) / p->tiles;
+    const uint64_t blocks = (S + B - 1) / B;
+    const uint64_t cut = std::min(wanted, blocks);
+    const uint64_t per = (S + cut - 1) / cut;
+    p->chunk_states = B * ((per + B - 1) / B);
+    p->chunks = (S + p->chunk_states - 1) / p->chunk_states;
+    p->groups = p->tiles * p->chunks;
+    p->work_partials = num_queries * p->chunks;
+    return FKS_OK;
+}
+
 }  // namespace fks_batch

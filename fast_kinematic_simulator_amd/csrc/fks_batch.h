@@ -159,6 +159,43 @@ fks_status plan_summary(SummaryPlan* p, int32_t robot_type, uint32_t width, cons
                         uint64_t num_groups, const uint32_t* labels, const double* targets, double reached_distance,
                         const fks_cluster_summary* out, std::string* why);
 
+/* The plan of a state selection (fks_select_states and its device entries): every refusal, and the
+ * decomposition of the device's search.  *table and *out are read when non-NULL; no pointer inside
+ * them or `queries` is dereferenced.
+ *
+ * The rule.  A workgroup of the search takes one tile of queries against one chunk of states.  A
+ * tile holds kSelectTile = 8 queries (the last tile of a call fewer), so tiles = ceil(J / 8).  The
+ * states are cut into `chunks` equal chunks of chunk_states, a multiple of kSelectThreads = 256:
+ * as many chunks as bring tiles x chunks to kSelectGroupsPerCu = 4 workgroups per compute unit, and
+ * never more than there are blocks of 256 states, so that every chunk holds a state:
+ *     wanted       = ceil(4 x compute_units / tiles)              (1 when the tiles alone fill the device)
+ *     chunk_states = 256 x ceil(ceil(S / min(wanted, ceil(S / 256))) / 256)
+ *     chunks       = ceil(S / chunk_states)
+ * A table of at most 256 states, or a call of at least 32 x compute_units queries, is searched in
+ * one chunk.  The result does not depend on the rule: partial results are reduced by (smaller d,
+ * then smaller i), which is associative and is the ascending scan's answer for any cut.  The
+ * workspace holds one partial (fksd::SelectPartial) per (query, chunk). */
+constexpr uint64_t kMaxSelectQueries = 1ull << 20;
+constexpr uint64_t kMaxSelectParticles = 65536;
+constexpr uint64_t kMaxSelectStarts = 1ull << 31; /* J x P */
+constexpr uint64_t kSelectGroupsPerCu = 4;
+struct SelectPlan {
+    uint64_t num_queries = 0; /* J */
+    uint64_t num_states = 0;  /* S */
+    uint32_t width = 0;       /* W */
+    uint32_t particles = 0;   /* P */
+    bool launch = false;      /* false: J == 0 */
+    bool draw = false;        /* starts or source is asked for */
+    uint32_t tile = 0;          /* queries per workgroup */
+    uint64_t tiles = 0;         /* ceil(J / tile) */
+    uint64_t chunk_states = 0;  /* states per chunk, a multiple of 256 */
+    uint64_t chunks = 0;        /* chunks per query */
+    uint64_t groups = 0;        /* tiles x chunks: the search's grid */
+    uint64_t work_partials = 0; /* J x chunks */
+};
+fks_status plan_select(SelectPlan* p, uint32_t width, int32_t compute_units, const fks_state_table* table, const double* queries,
+                       uint64_t num_queries, uint32_t num_particles, const fks_state_selection* out, std::string* why);
+
 }  // namespace fks_batch
 
 #endif

@@ -41,6 +41,10 @@ extern "C" __global__ void fks_cluster_se3(const fksd::ClusterArgs args);
 extern "C" __global__ void fks_summary_linked(const fksd::SummaryArgs args);
 extern "C" __global__ void fks_summary_se2(const fksd::SummaryArgs args);
 extern "C" __global__ void fks_summary_se3(const fksd::SummaryArgs args);
+extern "C" __global__ void fks_state_select_linked(const fksd::SelectArgs args);
+extern "C" __global__ void fks_state_select_se2(const fksd::SelectArgs args);
+extern "C" __global__ void fks_state_select_se3(const fksd::SelectArgs args);
+extern "C" __global__ void fks_state_draw(const fksd::SelectArgs args);
 extern "C" __global__ void fks_math_probe(const double* a, const double* b, double* out, uint64_t n);
 
 namespace {
@@ -258,6 +262,13 @@ struct fks_context {
      * (labels, then the outputs) */
     DeviceBuffer<double> d_summary_f64;
     DeviceBuffer<uint32_t> d_summary_u32;
+    /* fks_select_states_device: the search's partial results, one per (query, chunk) ... */
+    DeviceBuffer<fksd::SelectPartial> d_select_partials;
+    int32_t compute_units = 0; /* of the device, read at the first selection */
+    /* ... and the host entry's staging: every input and output array end to end, each on an 8-byte boundary, and
+     * the host copy of the inputs that goes up in one piece */
+    DeviceBuffer<double> d_select_stage;
+    std::vector<double> select_stage;
     MirroredBuffer<fksd::SimArgs> path_args; /* a batch's records (fks_batch::build_records): one per (job, leg) of
                                                 its normal form (a path's legs, a job batch's jobs), then job_first
                                                 and leg_first (SimArgs.job_first) */
@@ -1645,6 +1656,123 @@ fks_status fks_summarize_clusters_ctx(fks_context* ctx, const double* configs, c
     HIP_TRY(ctx, down_f(out->variances, d.variances, Wv));
     HIP_TRY(ctx, down_f(out->variance, d.variance, 1));
     HIP_TRY(ctx, down_u(out->reached, d.reached));
+    return FKS_OK;
+}
+
+/* The selection's two launches over device buffers, on one stream with nothing coming down in between: the search
+ * (one workgroup per query tile and chunk of states) and the draw (one workgroup per query), which is launched
+ * for a single chunk too.  No call index, no counters. */
+static fks_status select_device(fks_context* ctx, const fks_batch::SelectPlan& plan, const fks_state_table& d_table,
+                                const double* d_queries, uint64_t draw_seed, const fks_state_selection& d_out, hipStream_t s,
+                                int32_t synchronize) {
+    if (!plan.launch) return FKS_OK;
+    HIP_TRY(ctx, ctx->d_select_partials.reserve((size_t)plan.work_partials));
+    const uint64_t key = splitmix64(draw_seed);
+    fksd::SelectArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.R = ctx->R;
+    a.keys = d_table.keys;
+    a.weights = d_table.weights;
+    a.count = d_table.count;
+    a.begin = d_table.begin;
+    a.members = d_table.members;
+    a.num_states = plan.num_states;
+    a.num_member_rows = d_table.num_member_rows;
+    a.queries = d_queries;
+    a.num_queries = plan.num_queries;
+    a.particles = plan.draw ? plan.particles : 0u;
+    a.k0 = (uint32_t)key;
+    a.k1 = (uint32_t)(key >> 32);
+    a.chunk_states = plan.chunk_states;
+    a.chunks = plan.chunks;
+    a.partials = ctx->d_select_partials.get();
+    a.out_choice = d_out.choice;
+    a.out_distance = d_out.distance;
+    a.out_starts = d_out.starts;
+    a.out_source = d_out.source;
+    void (*kernel)(const fksd::SelectArgs) = ctx->R.type == FKS_ROBOT_LINKED
+                                                 ? fks_state_select_linked
+                                                 : (ctx->R.type == FKS_ROBOT_SE2 ? fks_state_select_se2 : fks_state_select_se3);
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)plan.groups), dim3(fksd::kSelectThreads), 0, s, a);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fks_state_draw, dim3((uint32_t)plan.num_queries), dim3(fksd::kSelectThreads), 0, s, a);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->pending = true;
+    ctx->pending_kind = 2;
+    ctx->pending_stream = s;
+    if (synchronize) return settle(ctx);
+    return FKS_OK;
+}
+
+/* what both context entries refuse, and the plan of what they run */
+static fks_status select_entry(fks_context* ctx, fks_batch::SelectPlan* plan, const fks_state_table* table, const double* queries,
+                               uint64_t num_queries, uint32_t num_particles, const fks_state_selection* out) {
+    if (!ctx) return FKS_ERR_INVALID_ARGUMENT;
+    if (!ctx->has_robot) return fail(ctx, FKS_ERR_NO_ROBOT, "fks_set_robot has not been called");
+    if (ctx->compute_units == 0)
+        HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    std::string why;
+    const fks_status st = fks_batch::plan_select(plan, (uint32_t)ctx->R.W, ctx->compute_units, table, queries, num_queries,
+                                                 num_particles, out, &why);
+    if (st != FKS_OK) return fail(ctx, st, why);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return settle(ctx);
+}
+
+fks_status fks_select_states_device(fks_context* ctx, const fks_state_table* d_table, const double* d_queries, uint64_t num_queries,
+                                    uint32_t num_particles, uint64_t draw_seed, const fks_state_selection* d_out, void* stream,
+                                    int32_t synchronize) {
+    fks_batch::SelectPlan plan;
+    const fks_status st = select_entry(ctx, &plan, d_table, d_queries, num_queries, num_particles, d_out);
+    if (st != FKS_OK) return st;
+    return select_device(ctx, plan, *d_table, d_queries, draw_seed, *d_out, reinterpret_cast<hipStream_t>(stream), synchronize);
+}
+
+fks_status fks_select_states_ctx(fks_context* ctx, const fks_state_table* table, const double* queries, uint64_t num_queries,
+                                 uint32_t num_particles, uint64_t draw_seed, const fks_state_selection* out) {
+    fks_batch::SelectPlan plan;
+    const fks_status st = select_entry(ctx, &plan, table, queries, num_queries, num_particles, out);
+    if (st != FKS_OK) return st;
+    if (!plan.launch) return FKS_OK;
+    const size_t W = plan.width, S = (size_t)plan.num_states, J = (size_t)plan.num_queries, P = plan.particles;
+    const size_t rows = plan.draw ? (size_t)table->num_member_rows : 0;
+    auto words = [](size_t n) { return (n + 1) / 2; }; /* doubles that hold n 32-bit words */
+    /* the inputs, in doubles from the staging's start: keys, queries, weights, members, count, begin; then the outputs */
+    const size_t i_keys = 0, i_queries = i_keys + S * W, i_weights = i_queries + J * W, i_members = i_weights + (table->weights ? S : 0),
+                 i_count = i_members + rows * W, i_begin = i_count + (table->count ? words(S) : 0),
+                 i_end = i_begin + (table->begin ? words(S) : 0);
+    const size_t o_choice = i_end, o_distance = o_choice + words(J), o_starts = o_distance + (out->distance ? J : 0),
+                 o_source = o_starts + (out->starts ? J * P * W : 0), o_end = o_source + (out->source ? words(J * P) : 0);
+    HIP_TRY(ctx, ctx->d_select_stage.reserve(o_end));
+    ctx->select_stage.resize(i_end);
+    double* h = ctx->select_stage.data();
+    std::memcpy(h + i_keys, table->keys, S * W * sizeof(double));
+    std::memcpy(h + i_queries, queries, J * W * sizeof(double));
+    if (table->weights) std::memcpy(h + i_weights, table->weights, S * sizeof(double));
+    if (rows) std::memcpy(h + i_members, table->members, rows * W * sizeof(double));
+    if (table->count) std::memcpy(h + i_count, table->count, S * sizeof(uint32_t));
+    if (table->begin) std::memcpy(h + i_begin, table->begin, S * sizeof(uint32_t));
+    double* d = ctx->d_select_stage.get();
+    HIP_TRY(ctx, hipMemcpy(d, h, i_end * sizeof(double), hipMemcpyHostToDevice));
+    fks_state_table dt = *table;
+    dt.keys = d + i_keys;
+    dt.weights = table->weights ? d + i_weights : nullptr;
+    dt.members = table->members ? d + i_members : nullptr;
+    dt.count = table->count ? reinterpret_cast<const uint32_t*>(d + i_count) : nullptr;
+    dt.begin = table->begin ? reinterpret_cast<const uint32_t*>(d + i_begin) : nullptr;
+    /* members that are given but not drawn from are not staged, and then not named either */
+    if (!plan.draw) dt.members = nullptr;
+    fks_state_selection ds;
+    ds.choice = reinterpret_cast<uint32_t*>(d + o_choice);
+    ds.distance = out->distance ? d + o_distance : nullptr;
+    ds.starts = out->starts ? d + o_starts : nullptr;
+    ds.source = out->source ? reinterpret_cast<uint32_t*>(d + o_source) : nullptr;
+    const fks_status run = select_device(ctx, plan, dt, d + i_queries, draw_seed, ds, nullptr, 1);
+    if (run != FKS_OK) return run;
+    HIP_TRY(ctx, hipMemcpy(out->choice, ds.choice, J * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out->distance) HIP_TRY(ctx, hipMemcpy(out->distance, ds.distance, J * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->starts) HIP_TRY(ctx, hipMemcpy(out->starts, ds.starts, J * P * W * sizeof(double), hipMemcpyDeviceToHost));
+    if (out->source) HIP_TRY(ctx, hipMemcpy(out->source, ds.source, J * P * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return FKS_OK;
 }
 

@@ -508,6 +508,44 @@ struct SummaryArgs {
     uint32_t* out_reached;
 };
 
+/* The argument of the selection kernels (fks_select_states_device: fks_state_select_<family>, then
+ * fks_state_draw): passed by value.  The search's workgroup b takes query tile b / chunks against
+ * chunk b % chunks of the states and stores one partial per (query, chunk) at
+ * partials[j * chunks + chunk]; the draw's workgroup j reduces query j's partials.  The table's and
+ * the selection's pointers are those of fks_state_table and fks_state_selection. */
+constexpr int kSelectThreads = 256; /* a workgroup of either kernel */
+#ifndef FKS_SELECT_TILE
+#define FKS_SELECT_TILE 8 /* (a build variant sets another: tools/select_bench.py times a tile of 1 against it) */
+#endif
+constexpr int kSelectTile = FKS_SELECT_TILE; /* queries of a workgroup of the search */
+constexpr int kDrawRows = 1024;     /* sources the draw keeps in LDS at a time */
+struct SelectPartial {
+    double d;   /* the smallest weighted distance of the chunk under the strict <, +inf for none */
+    uint32_t i; /* its state, FKS_STATE_NONE for none */
+    uint32_t pad;
+};
+struct SelectArgs {
+    RobotDev R;
+    const double* keys;
+    const double* weights;
+    const uint32_t* count;
+    const uint32_t* begin;
+    const double* members;
+    uint64_t num_states;
+    uint64_t num_member_rows;
+    const double* queries;
+    uint64_t num_queries;
+    uint32_t particles; /* P */
+    uint32_t k0, k1;    /* the draw's Philox key */
+    uint64_t chunk_states;
+    uint64_t chunks;
+    SelectPartial* partials;
+    uint32_t* out_choice;
+    double* out_distance;
+    double* out_starts;
+    uint32_t* out_source;
+};
+
 enum {
     kCntSuccessful = 0,
     kCntUnsuccessful,

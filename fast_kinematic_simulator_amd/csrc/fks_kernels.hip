@@ -4991,6 +4991,229 @@ extern "C" __global__ void __launch_bounds__(kSummaryThreads) fks_summary_se3(co
     summarize_groups<FKS_ROBOT_SE3>(args);
 }
 
+/* State selection (fks_select_states_device; the host twin is fks_select_states, the definition is
+ * in fks_capi.h), two launches on one stream.
+ *   search  fks_state_select_<family>: workgroup b of kSelectThreads takes query tile b / chunks
+ *           (kSelectTile queries, staged in LDS beside the joint table) against chunk b % chunks of
+ *           the states (fks_batch::plan_select).  Thread t takes states t, t + 256, ... of the chunk
+ *           and keeps one (d, i) per query of the tile in registers under the strict < from +inf: a
+ *           state's key, weight and count are loaded once and serve the tile's eight distances.
+ *           d is config_distance_of<RT>(cfg = key, target = query); for a linked robot the eight
+ *           sums run side by side over one pass of the dofs, each the expression tree of
+ *           config_distance_of.  Then the 64-lane butterfly by (smaller d, then smaller i) as in
+ *           policy_select, the four waves' pairs through LDS, and one partial per (query, chunk).
+ *   draw    fks_state_draw: workgroup j reduces query j's partials by the same rule, writes choice
+ *           and distance, computes the sources kDrawRows at a time into LDS and copies the rows
+ *           with consecutive threads on consecutive doubles.
+ * The rule is associative and equals the ascending scan's answer, so the result does not depend
+ * on the cut into chunks, threads or lanes. */
+__device__ __forceinline__ void select_merge(double& best, uint32_t& choice, double od, uint32_t oi) {
+    if (od < best || (od == best && oi < choice)) {
+        best = od;
+        choice = oi;
+    }
+}
+__device__ __forceinline__ void select_wave_min(double& best, uint32_t& choice) {
+#pragma unroll
+    for (int m = 1; m < kWave; m <<= 1) {
+        const double od = __shfl_xor(best, m, kWave);
+        const uint32_t oi = (uint32_t)__shfl_xor((int)choice, m, kWave);
+        select_merge(best, choice, od, oi);
+    }
+}
+template <int RT>
+__device__ __forceinline__ void select_states(const SelectArgs& A) {
+    constexpr uint32_t NT = kSelectThreads, NW = kSelectThreads / kWave, T = kSelectTile;
+    constexpr uint32_t KW = (RT == FKS_ROBOT_LINKED) ? 1u : (RT == FKS_ROBOT_SE2 ? 3u : 12u);
+    __shared__ double s_q[T * kMaxDofs];
+    __shared__ double s_joints[kJointWords * kMaxJoints];
+    __shared__ int32_t s_dofj[kMaxDofs];
+    __shared__ double s_red_d[NW * T];
+    __shared__ uint32_t s_red_i[NW * T];
+    __shared__ double s_d[(RT == FKS_ROBOT_SE3) ? T * NT : 1]; /* SE(3): a thread's distances to the tile's queries */
+    const RobotDev& R = A.R;
+    const uint32_t W = (uint32_t)R.W;
+    const uint32_t tid = threadIdx.x, ln = (uint32_t)lane_id(), wv = tid >> 6;
+    const double inf = __builtin_inf();
+    const JointDev* joints = R.joints;
+    const int32_t* dofj = R.dof_joint;
+    if constexpr (RT == FKS_ROBOT_LINKED) {
+        if (R.J <= kMaxJoints && R.D <= kMaxDofs) {
+            const double* sj = reinterpret_cast<const double*>(R.joints);
+            for (uint32_t k = tid; k < (uint32_t)(R.J * kJointWords); k += NT) s_joints[k] = gp(sj)[k];
+            for (uint32_t k = tid; k < (uint32_t)R.D; k += NT) s_dofj[k] = gp(R.dof_joint)[k];
+            joints = reinterpret_cast<const JointDev*>(s_joints);
+            dofj = s_dofj;
+        }
+    }
+    const uint64_t J = A.num_queries, S = A.num_states, chunks = A.chunks;
+    const uint64_t tile = (uint64_t)blockIdx.x / chunks, chunk = (uint64_t)blockIdx.x - tile * chunks;
+    const uint64_t j0 = tile * T;
+    if (j0 >= J) return; /* (the grid is tiles x chunks: never taken) */
+    /* the tile's queries; a tile past the last query repeats it and stores nothing for the repeats */
+    const double* Q = s_q;
+    if (W <= (uint32_t)kMaxDofs) {
+        for (uint32_t k = tid; k < T * W; k += NT) {
+            const uint32_t t = k / W, w = k - t * W;
+            const uint64_t j = (j0 + t < J) ? j0 + t : J - 1;
+            s_q[k] = gp(A.queries)[j * W + w];
+        }
+    } else {
+        Q = nullptr;
+    }
+    __syncthreads();
+    double best[T];
+    uint32_t choice[T];
+#pragma unroll
+    for (uint32_t t = 0; t < T; ++t) {
+        best[t] = inf;
+        choice[t] = FKS_STATE_NONE;
+    }
+    const uint64_t lo = chunk * A.chunk_states;
+    const uint64_t hi = (lo + A.chunk_states < S) ? lo + A.chunk_states : S;
+    for (uint64_t i = lo + tid; i < hi; i += NT) {
+        if (A.count && gp(A.count)[i] == 0u) continue;
+        const double* key = A.keys + i * W;
+        const double wgt = A.weights ? gp(A.weights)[i] : 1.0;
+        double d[T];
+        if constexpr (RT == FKS_ROBOT_LINKED) {
+            if (Q) {
+#pragma unroll
+                for (uint32_t t = 0; t < T; ++t) d[t] = 0.0;
+                for (int k = 0; k < RDIM(R, D); ++k) {
+                    const bool continuous = joints[dofj[k]].type == FKS_JOINT_CONTINUOUS;
+                    const double wk = gp(R.weights)[k], kv = gp(key)[k];
+#pragma unroll
+                    for (uint32_t t = 0; t < T; ++t) {
+                        const double raw = Q[t * W + k] - kv;
+                        const double sd = continuous ? fks_math::wrap_revolute(raw) : raw;
+                        const double e = wk * dabs(sd);
+                        d[t] = d[t] + e * e;
+                    }
+                }
+#pragma unroll
+                for (uint32_t t = 0; t < T; ++t) d[t] = dsqrt(d[t]);
+            } else {
+                for (uint32_t t = 0; t < T; ++t) {
+                    const uint64_t j = (j0 + t < J) ? j0 + t : J - 1;
+                    d[t] = config_distance_of<RT>(R, joints, dofj, key, A.queries + j * W);
+                }
+            }
+        } else {
+            double kv[KW];
+#pragma unroll
+            for (uint32_t k = 0; k < KW; ++k) kv[k] = gp(key)[k];
+            if constexpr (RT == FKS_ROBOT_SE3) {
+                /* one copy of the pose arithmetic, run once per query: eight copies side by side spill.  The
+                 * distances pass through the thread's own LDS column, so that the loop can stay rolled and
+                 * (best, choice) stay in registers */
+#pragma unroll 1
+                for (uint32_t t = 0; t < T; ++t) s_d[t * NT + tid] = config_distance_of<RT>(R, joints, dofj, kv, s_q + t * KW);
+#pragma unroll
+                for (uint32_t t = 0; t < T; ++t) d[t] = s_d[t * NT + tid];
+            } else {
+#pragma unroll
+                for (uint32_t t = 0; t < T; ++t) d[t] = config_distance_of<RT>(R, joints, dofj, kv, s_q + t * KW);
+            }
+        }
+#pragma unroll
+        for (uint32_t t = 0; t < T; ++t) {
+            const double dw = A.weights ? wgt * d[t] : d[t];
+            if (dw < best[t]) {
+                best[t] = dw;
+                choice[t] = (uint32_t)i;
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t t = 0; t < T; ++t) {
+        select_wave_min(best[t], choice[t]);
+        if (ln == 0) {
+            s_red_d[wv * T + t] = best[t];
+            s_red_i[wv * T + t] = choice[t];
+        }
+    }
+    __syncthreads();
+    if (tid < T && j0 + tid < J) {
+        double b = s_red_d[tid];
+        uint32_t c = s_red_i[tid];
+        for (uint32_t w = 1; w < NW; ++w) select_merge(b, c, s_red_d[w * T + tid], s_red_i[w * T + tid]);
+        FKS_GLOBAL SelectPartial* out = gpw(A.partials) + (j0 + tid) * chunks + chunk;
+        out->d = b;
+        out->i = c;
+        out->pad = 0u;
+    }
+}
+extern "C" __global__ void __launch_bounds__(kSelectThreads) fks_state_select_linked(const SelectArgs args) {
+    select_states<FKS_ROBOT_LINKED>(args);
+}
+extern "C" __global__ void __launch_bounds__(kSelectThreads) fks_state_select_se2(const SelectArgs args) {
+    select_states<FKS_ROBOT_SE2>(args);
+}
+extern "C" __global__ void __launch_bounds__(kSelectThreads) fks_state_select_se3(const SelectArgs args) {
+    select_states<FKS_ROBOT_SE3>(args);
+}
+/* the draw needs no robot type: the partials are pairs and the rows are bytes */
+extern "C" __global__ void __launch_bounds__(kSelectThreads) fks_state_draw(const SelectArgs A) {
+    constexpr uint32_t NT = kSelectThreads, NW = kSelectThreads / kWave;
+    __shared__ double s_d[NW];
+    __shared__ uint32_t s_i[NW];
+    __shared__ uint32_t s_member[kDrawRows];
+    const uint32_t W = (uint32_t)A.R.W, P = A.particles;
+    const uint32_t tid = threadIdx.x, ln = (uint32_t)lane_id(), wv = tid >> 6;
+    const bool draw = P > 0u && (A.out_starts || A.out_source);
+    for (uint64_t j = blockIdx.x; j < A.num_queries; j += gridDim.x) {
+        double best = __builtin_inf();
+        uint32_t choice = FKS_STATE_NONE;
+        const FKS_GLOBAL SelectPartial* part = gp(A.partials) + j * A.chunks;
+        for (uint64_t c = tid; c < A.chunks; c += NT) select_merge(best, choice, part[c].d, part[c].i);
+        select_wave_min(best, choice);
+        if (ln == 0) {
+            s_d[wv] = best;
+            s_i[wv] = choice;
+        }
+        __syncthreads();
+        best = s_d[0];
+        choice = s_i[0];
+        for (uint32_t w = 1; w < NW; ++w) select_merge(best, choice, s_d[w], s_i[w]);
+        if (tid == 0) {
+            gpw(A.out_choice)[j] = choice;
+            if (A.out_distance) gpw(A.out_distance)[j] = best;
+        }
+        if (draw) {
+            const uint64_t c = choice != FKS_STATE_NONE ? (uint64_t)gp(A.count)[choice] : 0ull;
+            const uint64_t b = choice != FKS_STATE_NONE ? (uint64_t)gp(A.begin)[choice] : 0ull;
+            /* every row read below lies in [b, b + c), inside the pool */
+            const bool none = choice == FKS_STATE_NONE || b + c > A.num_member_rows;
+            for (uint32_t base = 0; base < P; base += (uint32_t)kDrawRows) {
+                const uint32_t n = (P - base < (uint32_t)kDrawRows) ? P - base : (uint32_t)kDrawRows;
+                for (uint32_t k = tid; k < n; k += NT) {
+                    const uint32_t kk = base + k;
+                    uint32_t m = kk; /* c == P: the members in order */
+                    if (!none && c != (uint64_t)P) {
+                        uint32_t ctr[4] = {(uint32_t)j, kk >> 2, (uint32_t)(j >> 32), 0x44524157u};
+                        philox4x32_10(ctr, A.k0, A.k1);
+                        const uint32_t r = (kk & 3u) == 0u ? ctr[0] : ((kk & 3u) == 1u ? ctr[1] : ((kk & 3u) == 2u ? ctr[2] : ctr[3]));
+                        m = (uint32_t)(((uint64_t)r * c) >> 32); /* < c */
+                    }
+                    s_member[k] = m;
+                    if (A.out_source) gpw(A.out_source)[j * P + kk] = none ? FKS_STATE_NONE : (uint32_t)(b + m);
+                }
+                __syncthreads();
+                if (A.out_starts) {
+                    FKS_GLOBAL double* rows = gpw(A.out_starts) + (j * P + base) * W;
+                    for (uint32_t t = tid; t < n * W; t += NT) {
+                        const uint32_t k = t / W, w = t - k * W;
+                        rows[t] = none ? 0.0 : gp(A.members)[(b + s_member[k]) * W + w];
+                    }
+                }
+                __syncthreads(); /* the next rows reuse s_member */
+            }
+        }
+        __syncthreads(); /* the next query reuses s_d and s_i */
+    }
+}
+
 /* device self-test of the portable libm (fks_selftest_math) */
 extern "C" __global__ void fks_math_probe(const double* a, const double* b, double* out, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -764,6 +764,108 @@ class HipParticleContactSimulator:
             ctypes.c_void_p(stream or None), 1 if synchronize else 0)
         _capi.check(st, self._ctx, "fks_summarize_clusters_device")
 
+    def select_states(self, robot: RobotDescription, keys, queries, num_particles: int = 0, draw_seed: int = 0, weights=None,
+                      count=None, begin=None, members=None, outputs=None) -> dict:
+        """fks_select_states_ctx: for every query (J, W) the nearest of the states `keys` (S, W) under
+        the per-state `weights`, and the chosen state's members drawn into num_particles starts
+        (include/fks_capi.h).  Returns the arrays named in `outputs` (None: choice and distance, and
+        starts and source when num_particles > 0 and count, begin, members are given)."""
+        self.set_robot(robot)
+        call = _SelectCall(robot, keys, queries, num_particles, weights, count, begin, members, outputs)
+        st = self._lib.fks_select_states_ctx(self._ctx, ctypes.byref(call.table), *call.inputs(), ctypes.c_uint64(int(draw_seed)),
+                                             ctypes.byref(call.struct))
+        _capi.check(st, self._ctx, "fks_select_states_ctx")
+        return call.result()
+
+    def select_states_device(self, robot: RobotDescription, d_table: dict, num_states: int, d_queries, num_queries: int,
+                             num_particles: int, draw_seed: int, d_out: dict, num_member_rows: int = 0, stream=0, synchronize=False):
+        """fks_select_states_device: d_table holds device pointers (int) by name (keys, weights, count,
+        begin, members; absent or 0: NULL), e.g. the buffers successive summaries appended to; d_queries a
+        device pointer to (J, W) doubles; d_out device pointers by output name (SELECT_OUTPUTS).
+        `starts` is fit to be the next jobs call's starts by device pointer."""
+        self.set_robot(robot)
+        unknown = (set(d_table) - set(SELECT_TABLE)) | (set(d_out) - set(SELECT_OUTPUTS))
+        if unknown:
+            raise ValueError(f"unknown selection arrays {sorted(unknown)}")
+        table = _capi.StateTable(num_states=int(num_states), num_member_rows=int(num_member_rows),
+                                 **{name: (d_table.get(name) or None) for name in SELECT_TABLE})
+        struct = _capi.StateSelection(**{name: (d_out.get(name) or None) for name in SELECT_OUTPUTS})
+        st = self._lib.fks_select_states_device(
+            self._ctx, ctypes.byref(table), ctypes.c_void_p(d_queries or None), int(num_queries), int(num_particles),
+            ctypes.c_uint64(int(draw_seed)), ctypes.byref(struct), ctypes.c_void_p(stream or None), 1 if synchronize else 0)
+        _capi.check(st, self._ctx, "fks_select_states_device")
+
+
+# the arrays of a selection call, in the order of fks_state_table and fks_state_selection
+SELECT_TABLE = ("keys", "weights", "count", "begin", "members")
+SELECT_OUTPUTS = ("choice", "distance", "starts", "source")
+
+
+class _SelectCall:
+    """the host arrays of one selection call: the table, the queries, the outputs asked for and the structs that name them"""
+
+    def __init__(self, robot, keys, queries, num_particles, weights, count, begin, members, outputs):
+        W = robot.config_width
+        f64 = lambda a, shape: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+        u32 = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.uint32).reshape(-1))
+        self.keys, self.queries = f64(keys, (-1, W)), f64(queries, (-1, W))
+        self.weights, self.members = f64(weights, (-1,)), f64(members, (-1, W))
+        self.count, self.begin = u32(count), u32(begin)
+        S, J, P = self.keys.shape[0], self.queries.shape[0], int(num_particles)
+        for name, a in (("weights", self.weights), ("count", self.count), ("begin", self.begin)):
+            if a is not None and a.size != S:
+                raise ValueError(f"{name} must hold one entry per state")
+        self.J, self.P = J, P
+        if outputs is None:
+            drawn = P > 0 and all(a is not None for a in (count, begin, members))
+            outputs = ("choice", "distance") + (("starts", "source") if drawn else ())
+        unknown = set(outputs) - set(SELECT_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown selection outputs {sorted(unknown)}")
+        shapes = {"choice": ((J,), np.uint32), "distance": ((J,), np.float64), "starts": ((J, P, W), np.float64),
+                  "source": ((J, P), np.uint32)}
+        names = [n for n in SELECT_OUTPUTS if n in outputs]
+        # one spare element keeps a pointer non-NULL for an empty array
+        self.flat = {n: np.zeros(int(np.prod(shapes[n][0])) + 1, dtype=shapes[n][1]) for n in names}
+        self.shapes = {n: shapes[n][0] for n in names}
+        self.struct = _capi.StateSelection(**{n: self.flat[n].ctypes.data for n in names})
+        ptr = lambda a: None if a is None else a.ctypes.data
+        # (an empty members array is still a pool, of no rows: the spare keeps it non-NULL)
+        self._spare = np.zeros(1, dtype=np.float64)
+        members_ptr = None if self.members is None else (self.members.ctypes.data if self.members.size else self._spare.ctypes.data)
+        self.table = _capi.StateTable(keys=ptr(self.keys) if S else None, weights=ptr(self.weights), count=ptr(self.count),
+                                      begin=ptr(self.begin), members=members_ptr, num_states=S,
+                                      num_member_rows=0 if self.members is None else self.members.shape[0])
+
+    def inputs(self):
+        return (_cluster_ptr(self.queries, ctypes.c_double), self.J, self.P)
+
+    def result(self) -> dict:
+        return {n: a[:-1].reshape(self.shapes[n]).copy() for n, a in self.flat.items()}
+
+
+def select_states_host(robot: RobotDescription, keys, queries, num_particles: int = 0, draw_seed: int = 0, weights=None, count=None,
+                       begin=None, members=None, outputs=None) -> dict:
+    """fks_select_states: the host twin of Simulator.select_states, with the kernels' arithmetic and
+    without a context or a GPU; the same result byte for byte."""
+    call = _SelectCall(robot, keys, queries, num_particles, weights, count, begin, members, outputs)
+    desc, keep = robot.to_c()
+    st = _capi.lib().fks_select_states(ctypes.byref(desc), ctypes.byref(call.table), *call.inputs(), ctypes.c_uint64(int(draw_seed)),
+                                       ctypes.byref(call.struct))
+    del keep
+    _capi.check(st, None, "fks_select_states")
+    return call.result()
+
+
+def select_states_plan(num_queries: int, num_states: int, compute_units: int) -> dict:
+    """fks_select_states_plan: the decomposition of a device call (queries per workgroup, states per
+    chunk, chunks per query, workgroups of the search)."""
+    out = (ctypes.c_uint64 * 4)()
+    _capi.check(_capi.lib().fks_select_states_plan(int(num_queries), int(num_states), int(compute_units), out), None,
+                "fks_select_states_plan")
+    return {"tile": int(out[0]), "chunk_states": int(out[1]), "chunks": int(out[2]), "groups": int(out[3])}
+
+
 
 class _SummaryCall:
     """the host arrays of one summary call: inputs, the outputs asked for and the struct that names them"""

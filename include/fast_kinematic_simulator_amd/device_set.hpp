@@ -206,6 +206,21 @@ class DeviceSet {
         Check(fks_summarize_clusters_ctx(ctx_, configs, group_begin, num_groups, labels, targets, reached_distance, out), ctx_, what);
     }
 
+    /* the nearest state of a table for every query and the chosen states' members drawn into the
+     * next jobs' starts (fks_select_states_ctx, host buffers, its arguments): on devices[0] alone,
+     * as cluster_configs, and like it no batch of the simulation */
+    void select_states(const fks_state_table& table, const double* queries, uint64_t num_queries, uint32_t num_particles,
+                       uint64_t draw_seed, const fks_state_selection& out, const char* what) {
+        Check(fks_select_states_ctx(ctx_, &table, queries, num_queries, num_particles, draw_seed, &out), ctx_, what);
+    }
+    /* the same on device buffers of devices[0] (fks_select_states_device, its arguments) */
+    void select_states_device(const fks_state_table& d_table, const double* d_queries, uint64_t num_queries, uint32_t num_particles,
+                              uint64_t draw_seed, const fks_state_selection& d_out, void* stream, bool synchronize, const char* what) {
+        Check(fks_select_states_device(ctx_, &d_table, d_queries, num_queries, num_particles, draw_seed, &d_out, stream,
+                                       synchronize ? 1 : 0),
+              ctx_, what);
+    }
+
     /* many independent calls in one launch per device (fks_forward_simulate_jobs, host
      * buffers); the devices are chosen from the jobs' particles together as for simulate() */
     void simulate_jobs(const fks_job* jobs, uint64_t num_jobs, const char* what) {

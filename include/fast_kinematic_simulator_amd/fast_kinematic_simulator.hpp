@@ -134,6 +134,8 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
         std::uniform_int_distribution<uint64_t> seed_dist(0, std::numeric_limits<uint64_t>::max());
         rng_ = RNG(seed_dist(prng));
         dev_->reset_generators(prng_seed);
+        select_seed_ = prng_seed;
+        select_calls_ = 0;
     }
     RNG& GetRandomGenerator() override { return rng_; }
     std::map<std::string, double> GetStatistics() const override {
@@ -412,6 +414,39 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
         const DerivedRobotType& robot = Derived(immutable_robot);
         return fks::HipParticleContactSimulator::SummarizeClustersHost(robot.HipDescription(), FlatGroups(robot, groups), labels,
                                                                        FlatTargets(robot, targets), reached_distance);
+    }
+    /* Not part of SimulatorInterface: the planner's step between a summary and the next jobs
+     * (fks_select_states_ctx).  For every query the nearest state of `table` (flat rows, as
+     * SummarizeClusters returns them) under its weights, and the chosen state's members drawn into
+     * num_particles starts, in two launches on devices[0].  The draw seed is
+     * fks::SelectDrawSeed(prng_seed, k) for the k-th selection since ResetGenerators; no call index is
+     * consumed. */
+    fks::StateSelection SelectStates(const std::shared_ptr<BaseRobotType>& immutable_robot, const fks::StateTable& table,
+                                     const std::vector<Configuration, ConfigAlloc>& queries, const uint32_t num_particles = 0) {
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        SetRobot(robot);
+        const size_t W = (size_t)robot.HipDescription().ConfigurationWidth();
+        const std::vector<double> flat = fks::HipParticleContactSimulator::FlatQueries(FlatTargets(robot, queries), W);
+        fks::FlatStateSelection sel(table, queries.size(), num_particles, W, fks::SelectDrawSeed(select_seed_, select_calls_++));
+        dev_->select_states(table.View(W), flat.data(), queries.size(), num_particles, sel.out.draw_seed, sel.selection, "SelectStates");
+        return std::move(sel.out);
+    }
+    /* the same on device buffers of devices[0] (fks_select_states_device); returns the draw seed used */
+    uint64_t SelectStates(const std::shared_ptr<BaseRobotType>& immutable_robot, const fks_state_table& d_table, const double* d_queries,
+                          const uint64_t num_queries, const uint32_t num_particles, const fks_state_selection& d_out,
+                          void* stream = nullptr, const bool synchronize = true) {
+        SetRobot(Derived(immutable_robot));
+        const uint64_t seed = fks::SelectDrawSeed(select_seed_, select_calls_++);
+        dev_->select_states_device(d_table, d_queries, num_queries, num_particles, seed, d_out, stream, synchronize, "SelectStates");
+        return seed;
+    }
+    /* fks_select_states on the host, without a simulator: the same result byte for byte */
+    static fks::StateSelection SelectStatesHost(const std::shared_ptr<BaseRobotType>& immutable_robot, const fks::StateTable& table,
+                                                const std::vector<Configuration, ConfigAlloc>& queries, const uint32_t num_particles,
+                                                const uint64_t draw_seed) {
+        const DerivedRobotType& robot = Derived(immutable_robot);
+        return fks::HipParticleContactSimulator::SelectStatesHost(robot.HipDescription(), table, FlatTargets(robot, queries), num_particles,
+                                                                  draw_seed);
     }
     static std::vector<fks::Configuration> FlatTargets(const DerivedRobotType& robot, const std::vector<Configuration, ConfigAlloc>& targets) {
         std::vector<fks::Configuration> flat;
@@ -876,6 +911,7 @@ class HipParticleContactSimulator : public simple_simulator_interface::Simulator
     SimulatorSolverParameters solver_config_;
     double simulation_controller_frequency_;
     std::unique_ptr<fks::DeviceSet> dev_; /* the devices (DeviceSet: sharded batches, summed statistics) */
+    uint64_t select_seed_ = 0, select_calls_ = 0; /* SelectStates' draw seeds (fks::SelectDrawSeed) */
     fks_context* ctx_ = nullptr;          /* devices[0]: single-particle calls, small batches */
     mutable std::shared_ptr<const fks::RobotDescription> robot_key_;
     RNG rng_;

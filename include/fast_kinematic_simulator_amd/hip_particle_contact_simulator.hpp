@@ -208,6 +208,67 @@ struct FlatSummaryGroups {
 inline size_t SummaryVarianceWidth(const fks_robot_desc& d, size_t W) {
     return d.robot_type == FKS_ROBOT_LINKED ? W : (d.robot_type == FKS_ROBOT_SE2 ? 3 : 6);
 }
+/* The states SelectStates searches (fks_state_table in fks_capi.h), as flat rows: keys [S][W] (a
+ * summary's expectation rows), weights [S] or empty (every weight 1), count and begin [S] or empty (a
+ * summary's; begin an absolute row of members), members [rows][W] or empty. */
+struct StateTable {
+    std::vector<double> keys, weights, members;
+    std::vector<uint32_t> count, begin;
+    fks_state_table View(size_t W) const {
+        if (W == 0 || keys.size() % W != 0 || members.size() % W != 0) throw std::invalid_argument("rows of the wrong width");
+        const size_t S = keys.size() / W;
+        if ((!weights.empty() && weights.size() != S) || (!count.empty() && count.size() != S) || (!begin.empty() && begin.size() != S))
+            throw std::invalid_argument("one weight, count and begin per state");
+        fks_state_table t;
+        t.keys = keys.empty() ? nullptr : keys.data();
+        t.weights = weights.empty() ? nullptr : weights.data();
+        t.count = count.empty() ? nullptr : count.data();
+        t.begin = begin.empty() ? nullptr : begin.data();
+        t.members = members.empty() ? nullptr : members.data();
+        t.num_states = S;
+        t.num_member_rows = members.size() / W;
+        return t;
+    }
+};
+/* What SelectStates returns (fks_state_selection): choice and distance [J]; starts [J][P][W] and source
+ * [J][P] when the table has count, begin and members and P > 0, empty otherwise.  draw_seed is the seed
+ * the call drew with. */
+struct StateSelection {
+    size_t width = 0, particles = 0;
+    uint64_t draw_seed = 0;
+    std::vector<uint32_t> choice, source;
+    std::vector<double> distance, starts;
+};
+/* a selection's arrays sized for J queries, and the struct that names them */
+struct FlatStateSelection {
+    StateSelection out;
+    fks_state_selection selection;
+    FlatStateSelection(const StateTable& table, size_t J, size_t P, size_t W, uint64_t draw_seed) {
+        const bool drawn = P > 0 && !table.count.empty() && !table.begin.empty() && !table.members.empty();
+        out.width = W;
+        out.particles = drawn ? P : 0;
+        out.draw_seed = draw_seed;
+        out.choice.resize(J);
+        out.distance.resize(J);
+        if (drawn) {
+            out.starts.resize(J * P * W);
+            out.source.resize(J * P);
+        }
+        /* (a spare word for empty vectors: choice is required even for J == 0) */
+        selection.choice = out.choice.empty() ? &spare_u_ : out.choice.data();
+        selection.distance = out.distance.empty() ? &spare_d_ : out.distance.data();
+        selection.starts = drawn ? (out.starts.empty() ? &spare_d_ : out.starts.data()) : nullptr;
+        selection.source = drawn ? (out.source.empty() ? &spare_u_ : out.source.data()) : nullptr;
+    }
+    FlatStateSelection(const FlatStateSelection&) = delete; /* selection points into this object */
+    FlatStateSelection& operator=(const FlatStateSelection&) = delete;
+
+  private:
+    uint32_t spare_u_ = 0;
+    double spare_d_ = 0.0;
+};
+/* the draw seed of a simulator's k-th SelectStates since its generators were last reset */
+inline uint64_t SelectDrawSeed(uint64_t prng_seed, uint64_t k) { return prng_seed ^ (0x9E3779B97F4A7C15ull * (k + 1)); }
 /* What ForwardSimulateRobotsUnderPolicy returns: results[leg][particle] as a path's (a leg a
  * particle did not run holds the configuration it stopped at and no contact; target_config is
  * the chosen entry's action, or the configuration itself for such a leg), choices and distances
@@ -407,6 +468,7 @@ class HipParticleContactSimulator {
                                 const std::vector<int32_t>& devices)
         : dev_(environment, solver_config, simulation_controller_frequency, prng_seed, debug_level, devices) {
         ctx_ = dev_.primary();
+        select_seed_ = prng_seed;
         forward_steps_ = (uint32_t)std::max(1.0, solver_config.forward_simulation_time * simulation_controller_frequency);
         resolution_ = environment.collision_map.resolution;
         /* ResetGenerators (SPCS:457-471): the first per-thread generator */
@@ -539,7 +601,11 @@ class HipParticleContactSimulator {
     }
     void ResetStatistics() { dev_.reset_statistics(); }
     /* SPCS:457-471 */
-    void ResetGenerators(uint64_t prng_seed) { dev_.reset_generators(prng_seed); }
+    void ResetGenerators(uint64_t prng_seed) {
+        dev_.reset_generators(prng_seed);
+        select_seed_ = prng_seed;
+        select_calls_ = 0;
+    }
 
     /* ForwardSimulateRobots (SPCS:788-804).  display_fn is accepted for interface
      * parity; the batch path never draws (SPCS:801 passes enable_tracing=false). */
@@ -710,6 +776,52 @@ class HipParticleContactSimulator {
                                                      flat.labels.data(), flat.targets_or_null(), reached_distance, &flat.summary);
         if (st != FKS_OK) throw SimulatorError(st, std::string("SummarizeClustersHost: ") + fks_status_string(st));
         return std::move(flat.out);
+    }
+    /* The planner's step between a summary and the next jobs (fks_select_states_ctx): for every query the
+     * nearest state of `table` under its weights, and the chosen state's members drawn into P starts, in
+     * two launches.  queries are flat configurations.  The draw seed is SelectDrawSeed(prng_seed, k) for
+     * the k-th selection since the generators were last reset (StateSelection.draw_seed names it); no
+     * call index is consumed and no statistics move.  Byte for byte what SelectStatesHost returns for the
+     * same seed. */
+    StateSelection SelectStates(const RobotDescription& immutable_robot, const StateTable& table, const std::vector<Configuration>& queries,
+                                uint32_t num_particles = 0) {
+        SetRobot(immutable_robot);
+        const size_t W = (size_t)immutable_robot.ConfigurationWidth();
+        const std::vector<double> flat = FlatQueries(queries, W);
+        FlatStateSelection sel(table, queries.size(), num_particles, W, SelectDrawSeed(select_seed_, select_calls_++));
+        dev_.select_states(table.View(W), flat.data(), queries.size(), num_particles, sel.out.draw_seed, sel.selection, "SelectStates");
+        return std::move(sel.out);
+    }
+    /* the same on device buffers (fks_select_states_device): every pointer of d_table and d_out and d_queries
+     * are in HBM, d_out.starts fit to be the next jobs' starts; returns the draw seed used */
+    uint64_t SelectStates(const RobotDescription& immutable_robot, const fks_state_table& d_table, const double* d_queries,
+                          uint64_t num_queries, uint32_t num_particles, const fks_state_selection& d_out, void* stream = nullptr,
+                          bool synchronize = true) {
+        SetRobot(immutable_robot);
+        const uint64_t seed = SelectDrawSeed(select_seed_, select_calls_++);
+        dev_.select_states_device(d_table, d_queries, num_queries, num_particles, seed, d_out, stream, synchronize, "SelectStates");
+        return seed;
+    }
+    /* fks_select_states: the same on the host, with the kernels' arithmetic and without a simulator */
+    static StateSelection SelectStatesHost(const RobotDescription& robot, const StateTable& table, const std::vector<Configuration>& queries,
+                                           uint32_t num_particles, uint64_t draw_seed) {
+        const size_t W = (size_t)robot.ConfigurationWidth();
+        const fks_robot_desc d = robot.View();
+        const std::vector<double> flat = FlatQueries(queries, W);
+        FlatStateSelection sel(table, queries.size(), num_particles, W, draw_seed);
+        const fks_state_table t = table.View(W);
+        const fks_status st = fks_select_states(&d, &t, flat.data(), queries.size(), num_particles, draw_seed, &sel.selection);
+        if (st != FKS_OK) throw SimulatorError(st, std::string("SelectStatesHost: ") + fks_status_string(st));
+        return std::move(sel.out);
+    }
+    static std::vector<double> FlatQueries(const std::vector<Configuration>& queries, size_t W) {
+        std::vector<double> flat;
+        for (const Configuration& q : queries) {
+            if (q.size() != W) throw std::invalid_argument("query has the wrong width");
+            flat.insert(flat.end(), q.begin(), q.end());
+        }
+        if (flat.empty()) flat.push_back(0.0); /* a pointer for J == 0 */
+        return flat;
     }
     /* Many independent calls in one launch (fks_forward_simulate_jobs; no reference counterpart:
      * the planner's stream of small ForwardSimulateRobots / ReverseSimulateRobots calls, whose
@@ -948,6 +1060,7 @@ class HipParticleContactSimulator {
 
   private:
     DeviceSet dev_;
+    uint64_t select_seed_ = 0, select_calls_ = 0; /* SelectStates' draw seeds (SelectDrawSeed) */
     fks_context* ctx_ = nullptr; /* devices[0] */
     std::vector<unsigned char> robot_fingerprint_; /* the robot set last (RobotDescription::Fingerprint) */
     uint32_t forward_steps_ = 1; /* controller steps per simulation (SPCS:856): the trace's step capacity */

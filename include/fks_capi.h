@@ -703,6 +703,81 @@ fks_status fks_summarize_clusters_ctx(fks_context* ctx, const double* configs, c
                                       const uint32_t* labels, const double* targets, double reached_distance,
                                       const fks_cluster_summary* out);
 
+/* State selection (added within ABI 10): the planner's step between a summary and the next jobs
+ * call.  For each of J query configurations (the next sampled targets) the nearest state of a
+ * resident table is chosen, and the state's member particles become the P starts of job j, written
+ * where the next fks_job.starts reads them by device pointer; only the J indices have to come down.
+ * A table is what successive summaries appended into one pool: keys are their `expectation` rows,
+ * count and begin their `count` and `begin` (begin an absolute row of `members`).
+ *
+ * Selection of query q_j.  Configurations are taken as the bytes given: no ResetPosition, as in
+ * clustering.  d_i = weights[i] * config_distance(cfg = keys[i], target = q_j), one rounded product
+ * of the robot's configuration distance (config_distance_of<RT> on the device, fks_host_distance.h
+ * on the host: the same expression trees over the portable libm).  With weights == NULL the product
+ * is not formed, which equals all-1.0 weights bit for bit.  When count is given, a state with
+ * count[i] == 0 is no state (the empty-cluster rows of a summary).  The choice is the i of the
+ * smallest d_i under a strict < from +inf, scanned in ascending i: the lowest index wins a tie, a NaN
+ * distance never wins and neither does a NaN weight.  No winner gives choice = FKS_STATE_NONE and
+ * distance = +inf.  The caller folds the planner's feasibility and variance factors into weights.
+ * Parity with uncertainty_planning_core's StateDistance is not pinned: the entries are held to this
+ * statement and to nothing else.
+ *
+ * Draw of job j's starts, only when starts or source is asked for (it then needs P >= 1 and count,
+ * begin, members).  Let c = count[choice], b = begin[choice].  If c == P, source[j][k] = b + k: no
+ * draw, the members go over in order.  Otherwise source[j][k] = b + ((uint64_t)r_k * c >> 32), r_k
+ * word k & 3 of Philox4x32-10 at the counter {low32(j), k >> 2, high32(j), 0x44524157} under the key
+ * (k0, k1) = the low and high 32 bits of splitmix64(draw_seed) (x += 0x9E3779B97F4A7C15;
+ * x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31).
+ * Integer arithmetic only, so host and device agree by construction.  starts[j][k] is a byte copy
+ * of members[source[j][k]].  Job j's rows are source = FKS_STATE_NONE and every double +0.0 when
+ * the choice is FKS_STATE_NONE, or when b + c > num_member_rows (a guard against reading outside
+ * the pool; choice and distance are still reported).  draw_seed is the caller's: the call consumes
+ * no call index and moves no statistics, work counters or last-call counters.
+ *
+ * Limits and refusals.  S is 1 .. FKS_MAX_STATES, J at most 2^20, P at most 65,536, J x P at most
+ * 2^31.  Refused with FKS_ERR_INVALID_ARGUMENT before anything is staged: a NULL table or
+ * selection, NULL keys, S == 0 or above 2^30, NULL choice or queries with J > 0, starts or source
+ * asked for with P == 0 or with count, begin or members NULL, begin without count, J above 2^20, P
+ * above 65,536, J x P above 2^31, a malformed robot (host twin); FKS_ERR_NO_ROBOT for a context
+ * without a robot.  The device entries word every refusal in fks_get_last_error.  J == 0 succeeds
+ * and launches nothing. */
+#define FKS_STATE_NONE 0xFFFFFFFFu
+#define FKS_MAX_STATES (1ull << 30)
+typedef struct fks_state_table {
+    const double*   keys;      /* [S][W] the states' expectations (a summary's `expectation` rows) */
+    const double*   weights;   /* [S], or NULL (= every weight 1.0) */
+    const uint32_t* count;     /* [S] members of each state (a summary's `count`), or NULL */
+    const uint32_t* begin;     /* [S] first member row in `members` (a summary's `begin`), or NULL */
+    const double*   members;   /* [num_member_rows][W], or NULL */
+    uint64_t num_states;       /* S, 1 .. 2^30 */
+    uint64_t num_member_rows;
+} fks_state_table;
+typedef struct fks_state_selection {
+    uint32_t* choice;    /* [J] required */
+    double*   distance;  /* [J] may be NULL */
+    double*   starts;    /* [J][P][W] may be NULL */
+    uint32_t* source;    /* [J][P] may be NULL: the row of `members` each start is a copy of */
+} fks_state_selection;
+/* The host twin: no context, no GPU.  The device entries below equal it byte for byte. */
+fks_status fks_select_states(const fks_robot_desc* robot, const fks_state_table* table, const double* queries, uint64_t num_queries,
+                             uint32_t num_particles, uint64_t draw_seed, const fks_state_selection* out);
+/* The same in two launches on the caller's stream for the context's robot: the two structs are host
+ * structs, every pointer inside them and d_queries are in HBM.  Stream and synchronize as
+ * fks_forward_simulate_device.  The partial results of the search lie in a workspace the context
+ * owns, grown on demand and freed with the context. */
+fks_status fks_select_states_device(fks_context* ctx, const fks_state_table* d_table, const double* d_queries, uint64_t num_queries,
+                                    uint32_t num_particles, uint64_t draw_seed, const fks_state_selection* d_out, void* stream,
+                                    int32_t synchronize);
+/* The same on host buffers: one staged upload, one download per output array. */
+fks_status fks_select_states_ctx(fks_context* ctx, const fks_state_table* table, const double* queries, uint64_t num_queries,
+                                 uint32_t num_particles, uint64_t draw_seed, const fks_state_selection* out);
+/* The decomposition a device call of J queries against S states takes on a device of
+ * compute_units compute units (fks_batch::plan_select; no context, no GPU): out[0] queries per
+ * workgroup, out[1] states per chunk, out[2] chunks per query, out[3] workgroups of the search. */
+fks_status fks_select_states_plan(uint64_t num_queries, uint64_t num_states, int32_t compute_units, uint64_t out[4]);
+/* Philox4x32-10 as the draw uses it (the host's own; for tests): counter and key in, four words out */
+void fks_select_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+
 /* CheckConfigCollision (SPCS:1398-1416) for a batch of n configurations (host
  * buffers): SetPosition(config), CheckEnvironmentCollision at threshold
  * inflation_ratio * res (SPCS:1403, 921-981) and CheckSelfCollisions at extended
